@@ -12,8 +12,13 @@ one MI355X.  N > 1: the same 4096 streams on every GPU (weak scaling; streams
 are independent, no collective on the data path -- torch.distributed/RCCL is
 used only for the timing barrier and the max-over-ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly K steps in one region and prints the result line.
+--full adds what takes runs of its own: the median over repeated K-step regions, the copy ceiling,
+the 8192-stream point, the PCIe-inclusive rate, the CPU baselines and the secondary lines.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32).
 """
 import argparse
 import json
@@ -57,7 +62,32 @@ PMC_TRAFFIC_BYTES_PER_FRAME_PAIR = 7808 * (3.8648 / 3.8233) + 7.21875 * 1024
 # WRITE_SIZE 7.2567 KB (7 392 B of state and samples, the step counter, partial lines)
 PMC_TRAFFIC_BYTES_PER_FRAME_FLOW = 7808 * (3.6010 / 3.8292) + 7.2567 * 1024
 NS_PRIME_FRAMES = 250  # untimed set-up frames + warm-up >= this (start-up phase of ns_core.c is 200)
+# untimed steps ahead of a plain run's one timed region (priming + warm-up + settle) >= this: the chip comes out of the
+# host-side set-up at a low clock, and a few ms of steps do not bring it up (1000 steps read 13.9 us per step after
+# 250 warm-up steps, 12.5 us after 4000 steps)
+NS_SETTLE_STEPS = 4000
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 60 * 10**6  # --dump-outputs: array bytes in all (at most 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1, stream_axis=None):
+    """--dump-outputs: the arrays the last timed step handed its caller, one <out_dir>/<name>.npy each in
+    float32 (rank r of an N > 1 run: <name>_rank<r>.npy).  Streams run along axis 0 of every array (or the axis
+    `stream_axis` names for it); where the set would exceed DUMP_LIMIT_BYTES, the same fixed, seeded sample of
+    streams is kept from each array and its indices are written beside them (stream_index.npy, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    axis = dict(stream_axis or {})
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = min(a.shape[axis.get(k, 0)] for k, a in arrays.items())
+        keep = max(1, n * DUMP_LIMIT_BYTES // total - 1)
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: np.take(a, rows, axis=axis.get(k, 0)) for k, a in arrays.items()}
+        arrays["stream_index"] = rows.astype(np.float64)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), a)
 
 
 def host_cores():
@@ -194,13 +224,15 @@ def bench_bt(args):
     # timed region: `--steps` macroblock steps (the default 1000 = 117 ms at N = 1024).  A region costs 1-2 ms however long it
     # is (the chip's clock ramps up after the idle gap of the barrier; both builds show it: profiles/r04_region_length.txt),
     # so the 13 ms regions of earlier rounds (--steps / 10) read 12 % slower than the sustained rate
-    steps, warm = max(args.steps, 10), max(args.warmup // 10, 4)
+    steps, warm = args.steps, max(args.warmup // 10, 4)
     g.timed_steps(d_in.data_ptr(), d_out.data_ptr(), ring, warm)
     rank_barrier(dist)
     t0 = time.perf_counter()
     ev_ms = g.timed_steps(d_in.data_ptr(), d_out.data_ptr(), ring, steps)
     rank_barrier(dist)
     wall = time.perf_counter() - t0
+    if args.dump_outputs:   # the last step's macroblock of every stream-channel
+        dump_outputs(args.dump_outputs, {"bt%d_out" % n: d_out[(steps - 1) % ring].cpu().numpy()}, rank, world)
     ev_ms, wall = max_over_ranks(dist, [ev_ms, wall], device="cuda")   # the slowest rank's region
     if rank != 0:
         return finish_ranks(dist)
@@ -229,7 +261,7 @@ def bench_bt(args):
                      "macroblock_steps_per_launch": min(steps, 64) if bt_flow else 1,
                      "algorithmic_bytes_per_step": algo * S, "avg_step_us": launch_s * 1e6},
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # the CPU restatement (oracle/bt_oracle.c; the reference itself is unbuildable here, DESIGN.md
         # section 2), one stream-channel per thread; ctypes releases the GIL inside the C calls
         from concurrent.futures import ThreadPoolExecutor
@@ -276,7 +308,7 @@ def bench_split(args):
     def step(k):
         _check(g.lib.AspSplitBatch_Analysis(g.h, d_in[k % ring].data_ptr(), d_bands.data_ptr(), MEM_DEVICE), "Analysis")
         _check(g.lib.AspSplitBatch_Synthesis(g.h, d_bands.data_ptr(), d_out[k % ring].data_ptr(), MEM_DEVICE), "Synthesis")
-    steps, warm = max(args.steps // 4, 10), max(args.warmup // 10, 10)
+    steps, warm = args.steps, max(args.warmup // 10, 10)
     for k in range(warm):
         step(k)
     torch.cuda.synchronize()
@@ -285,6 +317,10 @@ def bench_split(args):
         step(k)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    if args.dump_outputs:   # the last step's bands and merged frame of every channel
+        dump_outputs(args.dump_outputs, {"split48_bands": d_bands.cpu().numpy(),
+                                         "split48_out": d_out[(steps - 1) % ring].cpu().numpy()},
+                     stream_axis={"split48_bands": 1})
     algo = 2 * (480 * 2 + 3 * 160 * 2)      # samples in / bands out and back, int16; filter state is a few hundred bytes more
     achieved = algo * Cn * steps / wall / 1e9
     line = {
@@ -339,7 +375,7 @@ def bench_aec(args):
             g.enable_reported_delay(0)
     # warm-up passes the start-up phase; timed region: `--steps` frames (the default 1000 = 79 ms; the 20 ms regions of
     # earlier rounds, --steps / 4, carry the same ~1 ms per-region cost as the BT line: profiles/r04_region_length.txt)
-    steps, warm = max(args.steps, 10), max(args.warmup // 2, 80)
+    steps, warm = args.steps, max(args.warmup // 2, 80)
     g.timed_steps(d_far.data_ptr(), d_near.data_ptr(), d_out.data_ptr(), 160, ring, warm)
     rank_barrier(dist)
     assert g.control().startup_phase == 0
@@ -348,6 +384,8 @@ def bench_aec(args):
     rank_barrier(dist)
     wall = time.perf_counter() - t0
     assert bool(torch.isfinite(d_out).all())
+    if args.dump_outputs:   # the last step's output frame of every stream
+        dump_outputs(args.dump_outputs, {"aec_out": d_out[(steps - 1) % ring].cpu().numpy()}, rank, world)
     ev_ms, wall = max_over_ranks(dist, [ev_ms, wall], device="cuda")   # the slowest rank's region
     if rank != 0:
         return finish_ranks(dist)
@@ -382,7 +420,7 @@ def bench_aec(args):
                      "frame_steps_per_launch": min(steps, 64) if flow else 1,
                      "algorithmic_bytes_per_step": algo * S, "avg_step_us": step_s * 1e6},
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         from tests import oracle_lib
         cores = host_cores()
         if oracle_lib.have_aec_ref():
@@ -433,7 +471,7 @@ def _secondary(args, workload, cpu_baseline=True):
     and library state never touch the headline measurement; returns its JSON line as a dict."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", str(args.secondary_steps),
-           "--warmup", str(args.secondary_warmup)]
+           "--warmup", str(args.secondary_warmup), "--full"]
     if args.no_cpu_baseline or not cpu_baseline:
         cmd.append("--no-cpu-baseline")
     try:
@@ -499,12 +537,19 @@ def ns_measure(args, S, rank, world, local_rank, dist):
     if args.warmup > 0:
         ns.timed_steps(d_in.data_ptr(), d_out.data_ptr(), ring, args.warmup)
     # the timed region: EXACTLY --steps fused frame steps between two barriers (+ device
-    # synchronisation), repeated R times so the median is stable at small --steps; each region is
-    # timed by hipEvents recorded on the launch stream around the K steps (the clock every number of
-    # the line uses) and by the host's wall clock around the same region (reported beside it)
-    R = args.regions if args.regions > 0 else max(5, min(200, -(-4000 // max(args.steps, 1))))
+    # synchronisation), once in a plain run; --full repeats it R times so the median is stable at small
+    # --steps.  Each region is timed by hipEvents recorded on the launch stream around the K steps (the
+    # clock every number of the line uses) and by the host's wall clock around the same region (reported beside it)
+    R = args.regions if args.regions > 0 else max(5, min(200, -(-4000 // max(args.steps, 1)))) if args.full else 1
     ev, wall, enq = [], [], []
-    ns.timed_steps(d_in.data_ptr(), d_out.data_ptr(), ring, args.steps)   # graph capture of the K-step region
+    settle = 0
+    if args.graph or args.full:
+        ns.timed_steps(d_in.data_ptr(), d_out.data_ptr(), ring, args.steps)   # graph capture of the K-step region
+    else:   # a plain run: untimed steps until NS_SETTLE_STEPS have run since set-up (a count, so dumps repeat)
+        settle = max(0, NS_SETTLE_STEPS - primed - args.warmup)
+        if settle:
+            ns.timed_steps(d_in.data_ptr(), d_out.data_ptr(), ring, settle)
+    ns_measure.settle_steps = settle
     for _ in range(R):
         barrier()
         t0 = time.perf_counter()
@@ -515,6 +560,8 @@ def ns_measure(args, S, rank, world, local_rank, dist):
         enq.append(ns.last_enqueue_us() / max(args.steps, 1))
     if not torch.isfinite(d_out).all():
         raise SystemExit("non-finite output")
+    # --dump-outputs: the last timed step's output frame of every stream (ring slot (K - 1) % ring)
+    ns_measure.last_output = d_out[(args.steps - 1) % ring].cpu().numpy() if args.dump_outputs else None
     ns.close()
     del d_in, d_out
     ns_measure.host_enqueue_us_per_step = float(np.median(enq))  # this rank's host budget per step
@@ -553,9 +600,15 @@ def main():
     ap.add_argument("--streams-per-gpu", type=int, default=0,
                     help="default: 4096 at --gpus 1 (BASELINE config 2), 8192 at --gpus > 1 (config 5: 65 536 streams on 8 GPUs)")
     ap.add_argument("--ring", type=int, default=100, help="distinct input frames resident in HBM")
-    ap.add_argument("--regions", type=int, default=0, help="repeats of the K-step timed region (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the AEC / BT-1024 / config-5 lines of the N = 1 run")
+    ap.add_argument("--regions", type=int, default=0,
+                    help="repeats of the K-step timed region (0 = auto: one in a plain run, 5-200 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: repeated timed regions, copy ceiling, config-5 and "
+                         "PCIe-inclusive points, CPU baselines, the AEC / BT-1024 / BT-256 lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the AEC / BT-1024 / config-5 lines of the N = 1 run")
     ap.add_argument("--graph", action="store_true", help="replay captured hipGraphs (one linear graph per chain) instead of plain launches")
     ap.add_argument("--no-graph", action="store_true", help="(default) plain kernel launches")
     ap.add_argument("--secondary-steps", type=int, default=1000)
@@ -574,6 +627,8 @@ def main():
     ap.add_argument("--workload", default="ns", choices=["ns", "bt1024", "bt256", "aec", "split48"],
                     help="ns = the headline metric (default); bt* / aec / split48 = secondary lines")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.streams_per_gpu <= 0:
         args.streams_per_gpu = 4096 if (args.gpus == 1 or args.workload != "ns") else 8192
     if args.workload == "aec":
@@ -589,6 +644,8 @@ def main():
     from audiosignalprocess_amd.shard import max_over_ranks
 
     ev, wall, S, primed = ns_measure(args, args.streams_per_gpu, rank, world, local_rank, dist)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ns_out": ns_measure.last_output}, rank, world)
     # per region: the slowest rank's time (MAX over ranks), then the median over regions
     ev = np.array(max_over_ranks(dist, list(ev), device="cuda"))
     wall = np.array(max_over_ranks(dist, list(wall), device="cuda"))
@@ -627,6 +684,7 @@ def main():
                 "total_streams": S * world,
                 "input_ring_frames": args.ring,
                 "primed_frames_in_setup": primed,
+                "settle_steps_in_setup": ns_measure.settle_steps,
                 "sub_launches_per_step": conc,
                 "frame_steps_per_launch": steps_per_launch,
                 "launch": ("hipGraph replay (one linear graph per chain, kernel nodes only)" if args.graph else "plain launches"),
@@ -668,7 +726,7 @@ def main():
                 "avg_launch_us": step_s * 1e6 * steps_per_launch,
             },
         }
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 cc, cc_small = copy_ceiling_gbs(local_rank)
                 line["roofline"]["copy_ceiling"] = cc
@@ -677,10 +735,10 @@ def main():
             except Exception as e:  # noqa: BLE001
                 line["roofline"]["copy_ceiling"] = None
                 line["roofline"]["copy_ceiling_error"] = str(e)[:200]
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             # BASELINE config 5 on one GPU (8192 streams): the like-for-like N = 1 point of the 8-GPU run
             a2 = argparse.Namespace(**vars(args))
-            a2.steps, a2.warmup, a2.regions = min(args.steps, 200), min(args.warmup, 50), 0
+            a2.steps, a2.warmup, a2.regions, a2.dump_outputs = min(args.steps, 200), min(args.warmup, 50), 0, None
             ev5, wall5, S5, _ = ns_measure(a2, 8192, 0, 1, local_rank, None)
             s5 = float(np.median(ev5)) / max(a2.steps, 1)
             line["config5_single_gpu"] = {
@@ -690,11 +748,11 @@ def main():
                 # what one rank of the 8-GPU run needs from its host core per step, beside the device time
                 "host_enqueue_us_per_step": ns_measure.host_enqueue_us_per_step,
             }
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             line["pcie_inclusive"] = pcie_inclusive(args.streams_per_gpu, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             torch.cuda.empty_cache()
             line["secondary"] = [_secondary(args, "aec"), _secondary(args, "bt1024"),
                                  _secondary(args, "bt256", cpu_baseline=False)]

@@ -253,6 +253,33 @@ class RefNs:
         self.lib.ref_ns_fft_tables(self._p(0), ip.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p))
         return ip, w
 
+    def window(self):
+        """The analysis / synthesis window stream 0 was initialised with (anaLen floats).  The one pointer of
+        NoiseSuppressionC (ns_core.h:52-114) is `window`, which WebRtcNs_InitCore points at a constant table of the
+        compiled reference: it is the only pointer-aligned word of the instance that dladdr places inside
+        libns_ref.so.  Read that way, it needs no accessor beyond what the probe has always exported."""
+        n = 128 if self.block == 80 else 256   # anaLen, ns_core.c:89-98
+        words = np.frombuffer(C.string_at(self.base, self.size), np.uint64)
+        lib = os.path.realpath(REF_SO)
+        hits = [int(w) for w in words if w and _dl_object(int(w)) == lib]
+        assert len(hits) == 1, "expected one pointer into %s in the instance, found %d" % (lib, len(hits))
+        return np.ctypeslib.as_array((C.c_float * n).from_address(hits[0])).copy()
+
+
+class _DlInfo(C.Structure):
+    _fields_ = [("dli_fname", C.c_char_p), ("dli_fbase", C.c_void_p),
+                ("dli_sname", C.c_char_p), ("dli_saddr", C.c_void_p)]
+
+
+def _dl_object(addr):
+    """Real path of the loaded shared object that holds address `addr` (dladdr), or None."""
+    dladdr = C.CDLL(None).dladdr
+    dladdr.argtypes = [C.c_void_p, C.POINTER(_DlInfo)]
+    info = _DlInfo()
+    if not dladdr(C.c_void_p(addr), C.byref(info)) or not info.dli_fname:
+        return None
+    return os.path.realpath(info.dli_fname.decode())
+
 
 # ------------------------------------------------------------ BlockThresholding
 from audiosignalprocess_amd._abi import AspBtState  # noqa: E402

@@ -4,7 +4,7 @@
 # three bench lines.   e.g. gpurun -- 'bash tools/ns_ab.sh "" "-DNS1_NT_STORE=1"'
 export TMPDIR=/tmp
 O=gpurun_out/ns_ab; mkdir -p $O
-B="--no-cpu-baseline --no-secondary --steps ${AB_STEPS:-400} --warmup 100"
+B="--full --no-cpu-baseline --no-secondary --steps ${AB_STEPS:-400} --warmup 100"
 for FLAGS in "$@"; do
   export ASP_HIPCC_EXTRA="ns_kernels1.hip:$FLAGS"
   touch audiosignalprocess_amd/csrc/ns_kernels1.hip

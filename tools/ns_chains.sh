@@ -5,7 +5,7 @@ O=gpurun_out/ns_chains; mkdir -p $O
 for split in 1 2 3 4; do
   for g in "" "--graph"; do
     for steps in 20 200; do
-      python3 bench.py --gpus 1 --steps $steps --warmup 5 --no-secondary --no-cpu-baseline --split $split $g > $O/s${split}_g${g#--}_k$steps.json 2>> $O/err.txt
+      python3 bench.py --full --gpus 1 --steps $steps --warmup 5 --no-secondary --no-cpu-baseline --split $split $g > $O/s${split}_g${g#--}_k$steps.json 2>> $O/err.txt
       python3 - <<PY
 import json
 d=json.load(open("$O/s${split}_g${g#--}_k$steps.json"))

@@ -8,8 +8,8 @@
 # launches (up to 64 frame steps each) and the plain build's (one step each) read alike.
 export TMPDIR=/tmp
 TAG=${1:-r04}; O=gpurun_out/$TAG; mkdir -p $O
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_steps20.json 2> $O/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/stats.json 2> $O/stats.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${TAG}_bench_steps20.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/stats.json 2> $O/stats.err
 cp $(ls $O/stats/*/*_kernel_stats.csv | head -1) $O/${TAG}_ns_kernel_stats.csv
 ARGS="--steps 40 --warmup 260 --no-cpu-baseline --no-secondary --split 1 --regions 5"
 i=0
@@ -55,9 +55,9 @@ for S in (4096,32768):
 print(res)
 PY
 for N in 1; do timeout -k 10 200 python3 tools/ns_flow_stamps.py 4096 8192; done > $O/${TAG}_ns_flow_stamps.txt 2>&1
-{ for S in 1024 2048 4096 8192 16384; do for F in on off; do python3 bench.py --no-cpu-baseline --no-secondary --steps 20 --warmup 5 --flow $F --streams-per-gpu $S 2>/dev/null | python3 -c "
+{ for S in 1024 2048 4096 8192 16384; do for F in on off; do python3 bench.py --full --no-cpu-baseline --no-secondary --steps 20 --warmup 5 --flow $F --streams-per-gpu $S 2>/dev/null | python3 -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('S %5d flow %-3s step_us %.2f (min %.2f) frac %.3f' % ($S, '$F', 1000*d['ms_per_step'], 1000*d['timing']['ms_per_step_min'], d['roofline']['frac']))"; done; done; } > $O/${TAG}_ns_size_sweep.txt 2>&1
-{ for K in 2 5 20 64 200 1000; do python3 bench.py --no-cpu-baseline --no-secondary --steps $K --warmup 5 2>/dev/null | python3 -c "
+{ for K in 2 5 20 64 200 1000; do python3 bench.py --full --no-cpu-baseline --no-secondary --steps $K --warmup 5 2>/dev/null | python3 -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('steps per timed region %4d: step_us %.2f (min %.2f) frac %.3f' % ($K, 1000*d['ms_per_step'], 1000*d['timing']['ms_per_step_min'], d['roofline']['frac']))"; done; } > $O/${TAG}_ns_steps_sweep.txt 2>&1
 tail -3 $O/${TAG}_ns_traffic.txt; head -3 $O/${TAG}_ns_kernel_stats.csv | cut -c1-200; cat $O/${TAG}_ns_size_sweep.txt $O/${TAG}_ns_steps_sweep.txt; python3 -c "
 import json; d=json.load(open('$O/${TAG}_bench_steps20.json')); print('step_us %.2f frac %.3f config5 %.3f' % (1000*d['ms_per_step'], d['roofline']['frac'], d['config5_single_gpu']['roofline_frac'])); print([ (s['workload'] if 'workload' in s else s.get('config',{}).get('workload','?'))[:30] + ' %.3f' % s['roofline']['frac'] for s in d['secondary']])"

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 TAG=${1:-v2}
 O=gpurun_out/profiles_$TAG; mkdir -p $O
 for W in aec bt1024; do
-  python3 bench.py --workload $W > $O/${ROUND:-r03}_${W}_${TAG}_bench.json 2> $O/${W}_bench.err
+  python3 bench.py --workload $W --full > $O/${ROUND:-r03}_${W}_${TAG}_bench.json 2> $O/${W}_bench.err
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/${W}_stats -- python3 bench.py --workload $W --no-cpu-baseline > $O/${W}_stats.json 2> $O/${W}_stats.err
   f=$(ls $O/${W}_stats/*/*_kernel_stats.csv | head -1); cp $f $O/${ROUND:-r03}_${W}_${TAG}_kernel_stats.csv; head -4 $O/${ROUND:-r03}_${W}_${TAG}_kernel_stats.csv | cut -c1-200
 done

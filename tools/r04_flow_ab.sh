@@ -7,7 +7,7 @@ timeout -k 10 900 python3 -m pytest tests/test_ns_gpu.py -x -q -k "handoff or ti
 tail -3 $O/flow_tests.log
 run() {  # tag, env...
   local tag=$1; shift
-  env "$@" timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_$tag.json 2> $O/bench_$tag.err || { tail $O/bench_$tag.err; exit 1; }
+  env "$@" timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_$tag.json 2> $O/bench_$tag.err || { tail $O/bench_$tag.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$O/bench_$tag.json')); print('$tag: step_us %.2f frac %.3f config5 %.3f' % (1000*d['ms_per_step'], d['roofline']['frac'], d['config5_single_gpu']['roofline_frac']))"
 }

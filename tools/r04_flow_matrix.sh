@@ -1,6 +1,6 @@
 #!/bin/bash
 # hand-off build: step time against the steps per timed region, the ring of resident input frames and the steps per launch
-B="--no-cpu-baseline --no-secondary --warmup 5"
+B="--full --no-cpu-baseline --no-secondary --warmup 5"
 one() { # label, env/args...
   local lab=$1; shift
   env "${ENVV[@]}" python3 bench.py $B "$@" 2>/dev/null | python3 -c "

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/r04; O=gpurun_out/r04
 timeout -k 10 900 python3 -m pytest tests/test_ns_gpu.py -x -q -k "handoff or timed_steps or pair_kernel or pair_then" > $O/k2_tests.log 2>&1 || { tail -30 $O/k2_tests.log; exit 1; }
 tail -2 $O/k2_tests.log
-B="--no-cpu-baseline --no-secondary --warmup 5"
+B="--full --no-cpu-baseline --no-secondary --warmup 5"
 for rep in 1 2; do
   for S in 4096 8192; do
     for K in 3 2; do

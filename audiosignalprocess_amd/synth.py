@@ -91,3 +91,48 @@ def aec_frames(num_streams, num_frames, stream0=0):
         return np.ascontiguousarray(a.astype(np.float32).reshape(num_streams, num_frames, 160).transpose(1, 0, 2))
 
     return shape(far), shape(near)
+
+
+def _lcg_u32(seeds, t0, count):
+    """The raw uint32 LCG words of _lcg_uniform (same recurrence), integer only: [S][count] uint32."""
+    seeds = np.asarray(seeds, dtype=np.uint32)
+    total = t0 + count
+    with np.errstate(over="ignore"):
+        a_pow = np.cumprod(np.full(total, _A, dtype=np.uint32), dtype=np.uint32)
+        geo = np.cumsum(np.concatenate(([np.uint32(1)], a_pow[:-1])), dtype=np.uint32)
+        c_t = (_C * geo).astype(np.uint32)
+        u = seeds[:, None] * a_pow[None, t0:] + c_t[None, t0:]
+    return u.astype(np.uint32)
+
+
+def vad_frames(num_streams, num_frames, fs, frame_ms, seed=0, stream0=0, frame0=0):
+    """VAD input, int16 [num_frames][num_streams][fs * frame_ms / 1000]; integer arithmetic only, so the
+    samples do not depend on the numpy version or on float rounding.
+
+    Per stream s and 10 ms block b (absolute block index, frame0 counted in frames of frame_ms):
+    a voiced burst (triangle of period fs / (110 + 13 (s mod 8)) plus noise, amplitude 1500..9000)
+    while ((b + 17 s) mod (60 + 4 (s mod 5))) < 25, else a noise floor of +-(24 .. 87); every 97th
+    block is all but silent (+-1), so the low-energy branch of the model is reached too.
+    """
+    L = fs * frame_ms // 1000
+    s = np.arange(stream0, stream0 + num_streams, dtype=np.int64)
+    seeds = ((12345 + 7919 * (s + 1000003 * seed)) & 0xFFFFFFFF).astype(np.uint32)
+    T = L * num_frames
+    t0 = L * frame0
+    u = _lcg_u32(seeds, t0, T).astype(np.int64)
+    n = (u >> 16) - 32768                                       # [-32768, 32767]
+    t = np.arange(t0, t0 + T, dtype=np.int64)[None, :]
+    b = t // (fs // 100)                                        # 10 ms block
+    period = (fs // (110 + 13 * (s % 8)))[:, None]
+    ph = t % period
+    tri = (np.abs(2 * 65536 * ph // period - 65536) - 32768)   # [-32768, 32768]
+    talk = ((b + 17 * s[:, None]) % (60 + 4 * (s[:, None] % 5))) < 25
+    amp = 1500 + ((b * 37 + 11 * s[:, None]) % 16) * 500
+    floor = 24 + (s[:, None] % 64)
+    voiced = (tri * amp) // 32768 + (n * (amp // 4)) // 32768
+    quiet = (n * floor) // 32768
+    hush = (b % 97) == 5
+    x = np.where(talk, voiced, quiet)
+    x = np.where(hush, (n >> 15), x)
+    x = np.clip(x, -32768, 32767).astype(np.int16)
+    return np.ascontiguousarray(x.reshape(num_streams, num_frames, L).transpose(1, 0, 2))

@@ -19,6 +19,7 @@
 #include "aec_layout.h"
 #include "asp_aec.h"
 #include "asp_ns.h"
+#include "handoff_host.h"
 
 using namespace aspaec;
 
@@ -280,21 +281,18 @@ struct AspAecBatch : AecCtl {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool dual = false;  // set only inside the K-step path
   // Hand-off build of the multi-frame entry points (Run on device buffers, TimedSteps; aec_kernels.hip,
-  // AecFlowArgs): while flow_rec is set the Process launches are not issued one by one but recorded as
-  // descriptors; up to kAecFlowMaxSteps of them go into ONE launch (grid y = step), in which a per-stream step
+  // AecFlowArgs; handoff.h): while flow_rec is set the Process launches are not issued one by one but recorded as
+  // descriptors; up to kHandoffMaxSteps of them go into ONE launch (grid y = step), in which a per-stream step
   // counter in memory orders a stream's consecutive steps.  -1 = default (on), 0 = off, 1 = on.
   int flow = -1;
   bool flow_rec = false;
   int flow_n = 0, flow_nr = 0;               // descriptors recorded so far; samples per call of the recording
   int flow_slot = 0;                         // ring of descriptor arrays: host (pinned) and device copies
-  unsigned char* flow_host = nullptr;        // [kAecFlowSlots][kAecFlowMaxSteps] AecFlowStep, or AecFlowStepAgn in the delay-agnostic mode
+  unsigned char* flow_host = nullptr;        // [kAecFlowSlots][kHandoffMaxSteps] AecFlowStep, or AecFlowStepAgn in the delay-agnostic mode
   unsigned char* flow_dev = nullptr;
   bool flow_agn = false;                     // the recording's element type
   hipEvent_t flow_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // slot i's launch has consumed its descriptors
-  unsigned* flow_seq = nullptr;              // [S] completed hand-off steps per stream (== flow_count between calls)
-  unsigned* flow_abort = nullptr;            // 16 B: word 0 != 0 after a wait timed out
-  unsigned flow_count = 0;
-  bool flow_unchecked = false;
+  HandoffSync sync;
   unsigned* flow_bits = nullptr;             // delay logging: [S][kFlowBitsBlocks][2] binary spectra of the recorded steps' blocks
   int flow_blocks = 0;                       // blocks of the recording so far (their spectra wait for aec_delay_bits_kernel)
   // Per-stream control (AspAecBatch_ProcessV / _InitStream): one control plane per stream on the host, the launch
@@ -366,14 +364,10 @@ int estimate_skew(const int* rawSkew, int size, int deviceSampleRateHz, float* s
 }  // namespace
 
 namespace {
-constexpr int kAecFlowMaxSteps = 64, kAecFlowSlots = 4;
-static_assert(kFlowBitsBlocks >= 4 * kAecFlowMaxSteps, "a step has at most four blocks");
-constexpr size_t kAecFlowElem = sizeof(AecFlowStepAgn);  // a slot holds kAecFlowMaxSteps elements of either type
+constexpr int kAecFlowSlots = 4;
+static_assert(kFlowBitsBlocks >= 4 * kHandoffMaxSteps, "a step has at most four blocks");
+constexpr size_t kAecFlowElem = sizeof(AecFlowStepAgn);  // a slot holds kHandoffMaxSteps elements of either type
 
-bool aec_flow_default() {
-  const char* e = getenv("ASP_AEC_FLOW");
-  return !(e && e[0] == '0');
-}
 // The delay-agnostic mode in one launch per call (aec_process_agn_kernel): one band, no echo metrics, the whole batch on
 // one control plane.  ASP_AEC_AGN_FUSED=0 keeps the launch-per-sub-frame form (the A / B switch).
 bool agn_fused(const AspAecBatch* b) {
@@ -387,7 +381,7 @@ bool agn_fused(const AspAecBatch* b) {
 // The hand-off build serves one band without skew compensation and echo metrics: the plain configuration, delay
 // logging (the estimator's launch follows each process launch) and the fused delay-agnostic mode.
 bool aec_flow_applies(const AspAecBatch* b, int steps) {
-  const bool on = b->flow < 0 ? aec_flow_default() : b->flow != 0;
+  const bool on = b->flow < 0 ? handoff_env_default("ASP_AEC_FLOW") : b->flow != 0;
   if (!b->per.empty()) return false;  // per-stream control: one far-end and one Process launch per call
   return on && steps >= 2 && !b->sim && b->num_high == 0 && !b->metricsMode &&
          (b->reported_delay_enabled || agn_fused(b)) && !b->skewMode && b->debug_stamps == nullptr;
@@ -395,15 +389,11 @@ bool aec_flow_applies(const AspAecBatch* b, int steps) {
 int aec_flow_resources(AspAecBatch* b) {
   if (b->delay_logging && b->flow_bits == nullptr)
     AEC_TRY(hipMalloc((void**)&b->flow_bits, (size_t)b->S * kFlowBitsBlocks * 2 * sizeof(unsigned)));
-  if (b->flow_seq) return 0;
-  AEC_TRY(hipMalloc((void**)&b->flow_seq, (size_t)b->S * sizeof(unsigned)));
-  AEC_TRY(hipMalloc((void**)&b->flow_abort, 16));
-  AEC_TRY(hipMemsetAsync(b->flow_seq, 0, (size_t)b->S * sizeof(unsigned), b->stream));
-  AEC_TRY(hipMemsetAsync(b->flow_abort, 0, 16, b->stream));
-  AEC_TRY(hipHostMalloc((void**)&b->flow_host, kAecFlowElem * kAecFlowSlots * kAecFlowMaxSteps, hipHostMallocDefault));
-  AEC_TRY(hipMalloc((void**)&b->flow_dev, kAecFlowElem * kAecFlowSlots * kAecFlowMaxSteps));
+  if (b->sync.seq) return 0;
+  AEC_TRY(b->sync.ensure(b->S, b->stream));
+  AEC_TRY(hipHostMalloc((void**)&b->flow_host, kAecFlowElem * kAecFlowSlots * kHandoffMaxSteps, hipHostMallocDefault));
+  AEC_TRY(hipMalloc((void**)&b->flow_dev, kAecFlowElem * kAecFlowSlots * kHandoffMaxSteps));
   for (int i = 0; i < kAecFlowSlots; ++i) AEC_TRY(hipEventCreateWithFlags(&b->flow_ev[i], hipEventDisableTiming));
-  b->flow_count = 0;
   b->flow_slot = 0;
   return 0;
 }
@@ -411,8 +401,8 @@ int aec_flow_resources(AspAecBatch* b) {
 int aec_flow_flush(AspAecBatch* b) {
   if (b->flow_n == 0) return 0;
   const int slot = b->flow_slot;
-  unsigned char* h = b->flow_host + (size_t)slot * kAecFlowMaxSteps * kAecFlowElem;
-  unsigned char* d = b->flow_dev + (size_t)slot * kAecFlowMaxSteps * kAecFlowElem;
+  unsigned char* h = b->flow_host + (size_t)slot * kHandoffMaxSteps * kAecFlowElem;
+  unsigned char* d = b->flow_dev + (size_t)slot * kHandoffMaxSteps * kAecFlowElem;
   const int n = b->flow_n;
   b->flow_n = 0;
   const bool agn = b->flow_agn;
@@ -420,14 +410,13 @@ int aec_flow_flush(AspAecBatch* b) {
   const int blocks = b->flow_blocks;  // > 0: delay logging is on
   b->flow_blocks = 0;
   AEC_TRY(launch_aec_process_flow(b->state, b->far_ring, b->tables, b->S, b->flow_nr, reinterpret_cast<const AecFlowStep*>(d), n,
-                                  b->flow_seq, b->flow_abort, b->flow_count, b->num_part, b->stream,
+                                  b->sync.seq, b->sync.abort, b->sync.count, b->num_part, b->stream,
                                   (agn || blocks > 0) ? b->dblocks : nullptr, blocks > 0 ? b->flow_bits : nullptr, agn));
   // the estimator's share of these steps (aec_core.c:1191-1203): one launch for all their blocks, from the binary
   // spectra the process kernel left
   if (blocks > 0) AEC_TRY(launch_aec_delay_bits(b->dblocks, b->flow_bits, b->S, blocks, 1, b->stream));
   AEC_TRY(hipEventRecord(b->flow_ev[slot], b->stream));
-  b->flow_count += (unsigned)n;
-  b->flow_unchecked = true;
+  b->sync.enqueued(n);
   b->flow_slot = (slot + 1) % kAecFlowSlots;
   // the next slot's previous launch must have read its descriptors before they are overwritten
   AEC_TRY(hipEventSynchronize(b->flow_ev[b->flow_slot]));
@@ -441,7 +430,7 @@ int aec_flow_record(AspAecBatch* b, const float* near_dev, float* out_dev, int n
   }
   b->flow_nr = n;
   b->flow_agn = agn != nullptr;
-  unsigned char* slot_base = b->flow_host + (size_t)b->flow_slot * kAecFlowMaxSteps * kAecFlowElem;
+  unsigned char* slot_base = b->flow_host + (size_t)b->flow_slot * kHandoffMaxSteps * kAecFlowElem;
   const int idx = b->flow_n++;
   AecFlowStepAgn* sa = agn ? reinterpret_cast<AecFlowStepAgn*>(slot_base) + idx : nullptr;
   AecFlowStep& st = agn ? sa->step : reinterpret_cast<AecFlowStep*>(slot_base)[idx];
@@ -455,21 +444,16 @@ int aec_flow_record(AspAecBatch* b, const float* near_dev, float* out_dev, int n
   st.spec_base = -1;
   if (b->delay_logging && agn == nullptr) {  // (the delay-agnostic mode runs the estimator in the process wave)
     st.spec_base = b->flow_blocks;
-    for (int j = 0; j < ops.nsub; ++j) b->flow_blocks += ops.sub[j].nblocks;  // <= 4 per step, kFlowBitsBlocks = 4 * kAecFlowMaxSteps
+    for (int j = 0; j < ops.nsub; ++j) b->flow_blocks += ops.sub[j].nblocks;  // <= 4 per step, kFlowBitsBlocks = 4 * kHandoffMaxSteps
   }
-  if (b->flow_n == kAecFlowMaxSteps) return aec_flow_flush(b);
+  if (b->flow_n == kHandoffMaxSteps) return aec_flow_flush(b);
   return 0;
 }
 // after the batch's stream has been synchronised: did a hand-off wait time out?
 int aec_flow_check(AspAecBatch* b) {
-  if (!b->flow_unchecked) return 0;
-  b->flow_unchecked = false;
-  unsigned a = 0;
-  AEC_TRY(hipMemcpy(&a, b->flow_abort, sizeof a, hipMemcpyDeviceToHost));
-  if (a == 0) return 0;
-  std::vector<unsigned> seq((size_t)b->S, b->flow_count);
-  AEC_TRY(hipMemcpy(b->flow_seq, seq.data(), seq.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-  AEC_TRY(hipMemset(b->flow_abort, 0, 16));
+  bool timed_out = false;
+  AEC_TRY(b->sync.check(b->S, &timed_out));
+  if (!timed_out) return 0;
   return aec_fail(ASP_ERR_HIP, "AEC hand-off wait timed out: frame steps were skipped, re-initialise the batch");
 }
 
@@ -1433,9 +1417,8 @@ int AspAecBatch_Free(AspAecBatch* b) {
   if (b->vfar_host) (void)hipHostFree(b->vfar_host);
   if (b->vfar_dev) (void)hipFree(b->vfar_dev);
   if (b->vev) (void)hipEventDestroy(b->vev);
-  if (b->flow_seq) (void)hipFree(b->flow_seq);
+  b->sync.release();
   if (b->flow_bits) (void)hipFree(b->flow_bits);
-  if (b->flow_abort) (void)hipFree(b->flow_abort);
   if (b->flow_dev) (void)hipFree(b->flow_dev);
   if (b->flow_host) (void)hipHostFree(b->flow_host);
   for (int i = 0; i < 4; ++i)

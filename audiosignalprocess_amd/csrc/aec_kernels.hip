@@ -23,11 +23,13 @@
 #include <hip/hip_runtime.h>
 
 #include "aec_estimator.h"
+#include "handoff.h"
 #include "ns_device.h"  // lean fp64 pow / sincos shared with the NS kernels
 #include "pk_f32.h"     // complex arithmetic as packed f32
 
 using namespace aspaec;
 using namespace asppk;
+using namespace asphandoff;
 
 #ifndef AEC_FILTERFAR_FIRST
 #define AEC_FILTERFAR_FIRST 1  // FilterFar ahead of the near FFT (0: behind it, its row loads in flight under the transform)
@@ -395,8 +397,7 @@ __device__ __forceinline__ int ring_idx(int pos, int i, int count) {
 // The stream's state block through a buffer resource: one descriptor in SGPRs, the row offset as the
 // scalar offset, the lane's dword as the only vector offset.  (With flat global addressing the compiler
 // kept a 64-bit VGPR address per state row alive across the whole block: 100 registers.)
-// AUX: the cache-policy operand of every access through the descriptor: 0, or kSc1 in the hand-off build (below).
-constexpr int kSc1 = 16;
+// AUX: the cache-policy operand of every access through the descriptor: 0, or kSc1 (handoff.h) in the hand-off build.
 template <int AUX>
 struct StateBufT {
   __amdgpu_buffer_rsrc_t r;
@@ -418,45 +419,17 @@ __device__ __forceinline__ void sst(const StateBufT<AUX>& b, int uni, int vec, f
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), b.r, vec * 4, uni * 4, AUX);
 }
 
-// ---- the hand-off build (FLOW): consecutive frame steps overlap on the chip (the scheme of ns_kernels1.hip).
-// One launch carries M consecutive WebRtcAec_Process calls (each with the BufferFarend call before it) of the
-// whole batch: blockIdx.y is the step, its descriptor steps[blockIdx.y] sits in device memory.  Workgroups are
-// dispatched in linear order (x fastest), so the wave that takes stream s in step j + 1 may wait for the one
-// that has stream s in step j: it is resident or done.  The hand-off is a word in memory: seq[s] = k + 1 stored
-// by the wave that finished stream s of step k, its stores drained first; polled by the wave of step k + 1
-// before its first access to the stream's state or far-ring slots.  Every access to what a stream's steps hand
-// each other -- the state block and the far ring -- is an sc1 access (write-through stores, L1-bypassing loads;
-// MI355X_MICROARCH.md, visibility).  Frames in / out and the tables are plain.  The wait is bounded: a wave that
-// gives up sets the abort word, which every later wait sees (aec_api.hip reports it).
+// ---- the hand-off build (FLOW; the protocol: handoff.h): one launch carries M consecutive WebRtcAec_Process calls
+// (each with the BufferFarend call before it) of the whole batch; blockIdx.y is the step, its descriptor
+// steps[blockIdx.y] sits in device memory.  What a stream's steps hand each other -- the state block and the far
+// ring -- is accessed sc1; frames in / out and the tables are plain.
 struct AecFlowArgs {
   const AecFlowStep* steps;  // [gridDim.y]
-  unsigned* seq;             // [num_streams]: hand-off steps stream s has completed
-  unsigned* abort_w;         // != 0: a wait timed out (1 + stream)
+  HandoffArgs hand;
   unsigned want;             // blockIdx.y == 0 is step `want` of every stream
   DelayBlock* est;           // delay logging: the streams' estimator blocks (their mean spectra are kept here) and the
   unsigned* bits;            // launch's binary spectra [stream][kFlowBitsBlocks][far, near]; nullptr: off
 };
-typedef __attribute__((address_space(1))) unsigned gu32;
-__device__ __forceinline__ bool flow_wait(const AecFlowArgs& fa, unsigned want, int stream, int lane) {
-  const gu32* f = (const gu32*)(fa.seq + stream);
-  unsigned spins = 0;
-  for (;;) {
-    const unsigned v = __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((unsigned)__builtin_amdgcn_readfirstlane((int)v) == want) break;
-    ++spins;
-    if ((spins & 63u) == 0u) {
-      const unsigned a = __hip_atomic_load((const gu32*)fa.abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__builtin_amdgcn_readfirstlane((int)a) != 0) return false;
-    }
-    if (spins > (1u << 17)) {
-      if (lane == 0) __hip_atomic_store((gu32*)fa.abort_w, 1u + (unsigned)stream, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-    __builtin_amdgcn_s_sleep(2);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the state loads below the poll
-  return true;
-}
 
 // The same into rows `re` / `im` (dword offsets) of a block behind a descriptor.
 template <int AUX>
@@ -1818,7 +1791,7 @@ __global__ __launch_bounds__(256, NP == kNumPartNormal ? AEC_WAVES : 3) void aec
   float* st = state + (size_t)stream * AecRows(NP).state_dwords;
   const float* nin = fs->nearend + (size_t)stream * nrOfSamples;
   float* o = fs->out + (size_t)stream * nrOfSamples;
-  if (!flow_wait(fa, want, stream, lane)) return;
+  if (!handoff_wait(fa.hand, want, stream, lane)) return;
   const int spec_base = fs->spec_base;
   float* bits = (fa.bits != nullptr && spec_base >= 0)
                     ? reinterpret_cast<float*>(fa.bits + ((size_t)stream * kFlowBitsBlocks + spec_base) * 2) : nullptr;
@@ -1833,8 +1806,8 @@ __global__ __launch_bounds__(256, NP == kNumPartNormal ? AEC_WAVES : 3) void aec
                                   fs->farend, fs->fops, nullptr, nullptr, nullptr, nullptr, bits, fa.est);
   }
   // publish: every store of this wave drained first
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (lane == 0) __hip_atomic_store((gu32*)(fa.seq + stream), want + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  handoff_drain();
+  if (lane == 0) handoff_publish(fa.hand.seq + stream, want);
 }
 
 // ---- per-stream control (AspAecBatch_ProcessV / _InitStream): every stream has its own descriptors, read from
@@ -1984,7 +1957,7 @@ hipError_t launch_aec_process_flow(float* state, float* far_ring, const AecTable
   if (num_part != kNumPartNormal && num_part != kNumPartMax) return hipErrorInvalidValue;
   const int gx = ((num_streams + 3) / 4 + 7) / 8 * 8;  // a multiple of 8: a stream's consecutive steps on one XCD's in-order share
   const dim3 grid(gx, steps);
-  const AecFlowArgs fa = {descs, seq, abort_w, want, est, bits};
+  const AecFlowArgs fa = {descs, {seq, abort_w}, want, est, bits};
   // agn: `descs` is an array of AecFlowStepAgn (the delay-agnostic mode: control steps and estimator in the wave)
   if (agn) {
     if (num_part == kNumPartNormal)

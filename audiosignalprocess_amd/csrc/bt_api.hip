@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "asp_bt.h"
+#include "handoff_host.h"
 #include "asp_ns.h"
 #include "bt_layout.h"
 
@@ -256,51 +257,36 @@ struct AspBtBatch {
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // Hand-off build of the multi-macroblock entry points (AspBtBatch_DenoiseBlocks, TimedSteps; bt_kernels8.hip,
-  // BtFlowArgs): up to 64 consecutive macroblocks of every stream-channel per launch, a per-stream counter in memory
-  // orders a stream-channel's overlap-add tails.  -1 = default (on for 256 / 1024-sample windows), 0 = off, 1 = on.
+  // BtFlowArgs; handoff.h): up to kHandoffMaxSteps consecutive macroblocks of every stream-channel per launch, a
+  // per-stream counter in memory orders a stream-channel's overlap-add tails.  -1 = default (on for 256 / 1024-sample
+  // windows), 0 = off, 1 = on.
   int flow = -1;
-  unsigned* flow_seq = nullptr;    // [S]
-  unsigned* flow_abort = nullptr;  // 16 B
-  unsigned flow_count = 0;
-  bool flow_unchecked = false;
+  HandoffSync sync;
 };
 
 namespace {
 bool bt_flow_applies(const AspBtBatch* b, int steps, const float* in, float* out) {
-  const char* e = getenv("ASP_BT_FLOW");
-  const bool on = b->flow < 0 ? !(e && e[0] == '0') : b->flow != 0;
+  const bool on = b->flow < 0 ? handoff_env_default("ASP_BT_FLOW") : b->flow != 0;
   // the tuned kernels' windows, 8-byte aligned frames (their 8-byte accesses), whole groups of four at 256 samples
   return on && steps >= 2 && !b->any && (b->win == 1024 || (b->win == 256 && b->S % 4 == 0)) &&
          ((uintptr_t)in & 7) == 0 && ((uintptr_t)out & 7) == 0;
 }
 int bt_flow_steps(AspBtBatch* b, const float* in, float* out, int ring, int steps) {
-  if (!b->flow_seq) {
-    BT_TRY(hipMalloc((void**)&b->flow_seq, (size_t)b->S * sizeof(unsigned)));
-    BT_TRY(hipMalloc((void**)&b->flow_abort, 16));
-    BT_TRY(hipMemsetAsync(b->flow_seq, 0, (size_t)b->S * sizeof(unsigned), b->stream));
-    BT_TRY(hipMemsetAsync(b->flow_abort, 0, 16, b->stream));
-    b->flow_count = 0;
-  }
+  BT_TRY(b->sync.ensure(b->S, b->stream));
   const size_t per = (size_t)b->S * b->macro;
-  for (int k = 0; k < steps; k += 64) {
-    const int m = steps - k < 64 ? steps - k : 64;
-    BT_TRY(launch_bt_macroblock8_flow(b->win == 256, b->state, b->tables, in, out, b->S, b->macro, b->stream, b->flow_seq,
-                                      b->flow_abort, b->flow_count, m, k % ring, ring, per));
-    b->flow_count += (unsigned)m;
+  for (int k = 0; k < steps; k += kHandoffMaxSteps) {
+    const int m = steps - k < kHandoffMaxSteps ? steps - k : kHandoffMaxSteps;
+    BT_TRY(launch_bt_macroblock8_flow(b->win == 256, b->state, b->tables, in, out, b->S, b->macro, b->stream, b->sync.seq,
+                                      b->sync.abort, b->sync.count, m, k % ring, ring, per));
+    b->sync.enqueued(m);
   }
-  b->flow_unchecked = true;
   return ASP_OK;
 }
 // after the batch's stream has been synchronised: did a hand-off wait time out?
 int bt_flow_check(AspBtBatch* b) {
-  if (!b->flow_unchecked) return ASP_OK;
-  b->flow_unchecked = false;
-  unsigned a = 0;
-  BT_TRY(hipMemcpy(&a, b->flow_abort, sizeof a, hipMemcpyDeviceToHost));
-  if (a == 0) return ASP_OK;
-  std::vector<unsigned> seq((size_t)b->S, b->flow_count);
-  BT_TRY(hipMemcpy(b->flow_seq, seq.data(), seq.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-  BT_TRY(hipMemset(b->flow_abort, 0, 16));
+  bool timed_out = false;
+  BT_TRY(b->sync.check(b->S, &timed_out));
+  if (!timed_out) return ASP_OK;
   return bt_fail(ASP_ERR_HIP, "BT hand-off wait timed out: overlap-add tails were skipped, reset the batch");
 }
 }  // namespace
@@ -353,8 +339,7 @@ int AspBtBatch_Free(AspBtBatch* b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->state) (void)hipFree(b->state);
   if (b->any_block) (void)hipFree(b->any_block);
-  if (b->flow_seq) (void)hipFree(b->flow_seq);
-  if (b->flow_abort) (void)hipFree(b->flow_abort);
+  b->sync.release();
   if (b->stage_in) (void)hipFree(b->stage_in);
   if (b->stage_out) (void)hipFree(b->stage_out);
   if (b->ev0) (void)hipEventDestroy(b->ev0);

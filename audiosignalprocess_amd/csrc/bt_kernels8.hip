@@ -30,10 +30,12 @@
 #include <hip/hip_runtime.h>
 
 #include "bt_layout.h"
+#include "handoff.h"
 #include "pk_f32.h"
 
 using namespace aspbt;
 using namespace asppk;
+using namespace asphandoff;
 
 namespace {
 
@@ -549,19 +551,14 @@ __device__ __forceinline__ void scan_rows_full(const float (&pw)[8], int lastlan
 // step; its input / output is ring slot (slot0 + step) % ring).  What a stream-channel's consecutive macroblocks hand
 // each other is small: the input tail IS the last half window of the previous macroblock's input (read from there,
 // no hand-off; only the launch's first step reads the state's copy and only its last step writes it), and the
-// overlap-add tail, written by wave 7 at the very end of a macroblock and read by wave 0 of the next one just before
-// its own overlap-add -- ordered by a per-stream step counter in memory (sc1 stores drained, then the counter; wave 0
-// polls it, then sc1 loads), as in ns_kernels1.hip.  Workgroups are dispatched in grid order, so the macroblock
-// waited for has been dispatched a whole step earlier.  A wait that times out sets the abort word and the workgroup
-// carries on with a zero tail (the barriers that follow need every wave); bt_api.hip reports it.
+// overlap-add tail, written (sc1) by wave 7 at the very end of a macroblock and read (sc1) by wave 0 of the next one
+// just before its own overlap-add, behind the per-stream step counter of handoff.h.
 struct BtFlowArgs {
-  unsigned* seq;      // [num_streams]: macroblocks stream s has completed in hand-off launches
-  unsigned* abort_w;
+  HandoffArgs hand;   // seq[s]: macroblocks stream-channel s has completed in hand-off launches
   unsigned want;      // blockIdx.y == 0 is macroblock `want` of every stream
   int slot0, ring;
   unsigned per;       // floats between two ring slots of in / out
 };
-typedef __attribute__((address_space(1))) unsigned bt_gu32;
 typedef __attribute__((address_space(1))) unsigned long long bt_gu64;
 __device__ __forceinline__ f32x2 ld2_sc1(const float* p) {
   const unsigned long long v = __hip_atomic_load((const bt_gu64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -807,25 +804,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, 
   if (wave == 0) {
     if constexpr (FLOW) {
       // the stream-channel's previous macroblock must have published its overlap-add tail (Q4: four stream-channels)
-      const bt_gu32* f = (const bt_gu32*)(fa.seq + (Q4 ? g4 + (lane & 3) : (size_t)blockIdx.x));
-      bool ok = true;
-      for (unsigned spins = 0;;) {
-        const unsigned v = __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__all(v == flow_want)) break;
-        ++spins;
-        if ((spins & 63u) == 0u &&
-            __builtin_amdgcn_readfirstlane((int)__hip_atomic_load((const bt_gu32*)fa.abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) {
-          ok = false;
-          break;
-        }
-        if (spins > (1u << 17)) {
-          if (lane == 0) __hip_atomic_store((bt_gu32*)fa.abort_w, 1u + (unsigned)blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = false;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      // (a wait given up leaves a zero tail: the workgroup carries on, the barriers that follow need every wave)
+      const bool ok = handoff_wait_lanes(fa.hand, flow_want, Q4 ? g4 + (lane & 3) : (size_t)blockIdx.x, true,
+                                         blockIdx.x, lane);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         tail[j] = f32x2{0.0f, 0.0f};
@@ -889,8 +870,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, 
         else *reinterpret_cast<f32x2*>(dst) = f32x2{0.0f, 0.0f} + v[2 * q + 1];
       }
       if constexpr (FLOW) {  // publish the four stream-channels' macroblock: the tail stores drained first
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane < 4) __hip_atomic_store((bt_gu32*)(fa.seq + g4 + lane), flow_want + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        handoff_drain();
+        if (lane < 4) handoff_publish(fa.hand.seq + g4 + lane, flow_want);
       }
     }
   } else {
@@ -923,8 +904,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, 
       else *reinterpret_cast<f32x2*>(dst) = f32x2{0.0f, 0.0f} + v[j];
     }
     if constexpr (FLOW) {  // publish the stream-channel's macroblock: the tail stores drained first
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0) __hip_atomic_store((bt_gu32*)(fa.seq + blockIdx.x), flow_want + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      handoff_drain();
+      if (lane == 0) handoff_publish(fa.hand.seq + blockIdx.x, flow_want);
     }
   }
   }
@@ -983,7 +964,7 @@ namespace aspbt {
 hipError_t launch_bt_macroblock8(float* state, const BtTables* T, const float* in, float* out,
                                  int num_streams, int in_stride, int out_stride, hipStream_t s,
                                  unsigned long long* stamps) {
-  const BtFlowArgs none = {nullptr, nullptr, 0u, 0, 1, 0u};
+  const BtFlowArgs none = {{nullptr, nullptr}, 0u, 0, 1, 0u};
   hipLaunchKernelGGL((bt_macroblock8_kernel<false, false>), dim3(num_streams), dim3(512), 0, s, state, T, in, out,
                      in_stride, out_stride, stamps, none);
   return hipGetLastError();
@@ -991,7 +972,7 @@ hipError_t launch_bt_macroblock8(float* state, const BtTables* T, const float* i
 
 hipError_t launch_bt_macroblock8_q4(float* state, const BtTables* T, const float* in, float* out, int groups,
                                     int in_stride, int out_stride, hipStream_t s) {
-  const BtFlowArgs none = {nullptr, nullptr, 0u, 0, 1, 0u};
+  const BtFlowArgs none = {{nullptr, nullptr}, 0u, 0, 1, 0u};
   hipLaunchKernelGGL((bt_macroblock8_kernel<true, false>), dim3(groups), dim3(512), 0, s, state, T, in, out, in_stride,
                      out_stride, (unsigned long long*)nullptr, none);
   return hipGetLastError();
@@ -1003,7 +984,7 @@ hipError_t launch_bt_macroblock8_q4(float* state, const BtTables* T, const float
 hipError_t launch_bt_macroblock8_flow(bool q4, float* state, const BtTables* T, const float* in, float* out, int num_streams,
                                       int stride, hipStream_t s, unsigned* seq, unsigned* abort_w, unsigned want, int steps,
                                       int slot0, int ring, size_t per) {
-  const BtFlowArgs fa = {seq, abort_w, want, slot0, ring, (unsigned)per};
+  const BtFlowArgs fa = {{seq, abort_w}, want, slot0, ring, (unsigned)per};
   if (q4)
     hipLaunchKernelGGL((bt_macroblock8_kernel<true, true>), dim3(num_streams / 4, steps), dim3(512), 0, s, state, T, in, out,
                        stride, stride, (unsigned long long*)nullptr, fa);

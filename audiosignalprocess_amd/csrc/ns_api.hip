@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "asp_ns.h"
+#include "handoff_host.h"
 #include "ns_layout.h"
 
 using namespace aspns;
@@ -619,14 +620,11 @@ struct AspNsBatch {
   unsigned long long* timeline = nullptr;  // diagnostic (AspNsBatch_DebugTimeline): [workgroup][4] real-time stamps
   unsigned long long* flow_stamps = nullptr;  // diagnostic (AspNsBatch_DebugFlowStamps): 17 phase stamps of one wave
   double last_enqueue_us = 0.0;  // host time the last TimedSteps call spent enqueuing its launches
-  // Hand-off build of the multi-step entry points (ns_kernels1.hip, NsFlowArgs): up to kFlowMaxSteps
-  // consecutive frame steps of a K-step call per launch; a per-stream step counter in memory orders step
-  // k + 1 of a stream behind its step k.  -1 = default (on for the pair-layout kernel), 0 = off, 1 = on.
+  // Hand-off build of the multi-step entry points (handoff.h; ns_kernels1.hip, NsFlowArgs): up to
+  // kHandoffMaxSteps consecutive frame steps of a K-step call per launch; a per-stream step counter in memory
+  // orders step k + 1 of a stream behind its step k.  -1 = default (on for the pair-layout kernel), 0 = off, 1 = on.
   int flow = -1;
-  unsigned* flow_seq = nullptr;    // [S] completed hand-off steps per stream (== flow_count between calls)
-  unsigned* flow_abort = nullptr;  // 16 B: word 0 != 0 after a wait timed out
-  unsigned flow_count = 0;         // hand-off steps enqueued so far
-  bool flow_unchecked = false;     // hand-off launches enqueued since the abort word was last read
+  HandoffSync sync;
   // > 16 kHz: 1 or 2 high bands next to the low band (ns_core.c:1362-1414)
   uint32_t fs = 16000;
   int block = kBlockL;  // samples per frame and stream: 160, or 80 at 8 kHz (ns_core.c:89-98)
@@ -723,8 +721,7 @@ int AspNsBatch_Free(AspNsBatch* b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->state) (void)hipFree(b->state);
   if (b->hist) (void)hipFree(b->hist);
-  if (b->flow_seq) (void)hipFree(b->flow_seq);
-  if (b->flow_abort) (void)hipFree(b->flow_abort);
+  b->sync.release();
   if (b->stage_in) (void)hipFree(b->stage_in);
   if (b->stage_out) (void)hipFree(b->stage_out);
   if (b->hb_tail) (void)hipFree(b->hb_tail);
@@ -875,68 +872,42 @@ static int chain_parts(const AspNsBatch* b, int base[5]) {
   return parts;
 }
 
-static bool flow_default() {
-  const char* e = getenv("ASP_NS_FLOW");
-  return !(e && e[0] == '0');
-}
-
 // The hand-off build serves a K-step call of a batch in the fused representation on the pair-layout kernel.
 static bool flow_applies(const AspNsBatch* b, int steps) {
-  const bool on = b->flow < 0 ? flow_default() : b->flow != 0;
+  const bool on = b->flow < 0 ? handoff_env_default("ASP_NS_FLOW") : b->flow != 0;
   // (the two-streams-per-wave kernel addresses the whole state array through one 32-bit buffer offset)
   if (b->kernel == 2 && (size_t)b->S * kStreamDwords * 4 >= ((size_t)1 << 32)) return false;
   return on && steps >= 2 && b->paired && b->kernel != 1 && b->fs != 8000 && b->timeline == nullptr;
 }
 
-static int flow_resources(AspNsBatch* b) {
-  if (!b->flow_seq) {
-    HIP_TRY(hipMalloc((void**)&b->flow_seq, (size_t)b->S * sizeof(unsigned)));
-    HIP_TRY(hipMalloc((void**)&b->flow_abort, 16));
-    HIP_TRY(hipMemsetAsync(b->flow_seq, 0, (size_t)b->S * sizeof(unsigned), b->stream));
-    HIP_TRY(hipMemsetAsync(b->flow_abort, 0, 16, b->stream));
-    b->flow_count = 0;
-  }
-  return ASP_OK;
-}
-
-// K steps of the hand-off build on the batch's stream: launches of up to kFlowMaxSteps consecutive frame
+// K steps of the hand-off build on the batch's stream: launches of up to kHandoffMaxSteps consecutive frame
 // steps each (grid y = step); launches follow each other in stream order.
-constexpr int kFlowMaxSteps = 64;
 static int flow_steps(AspNsBatch* b, const float* din, float* dout, int ring, int steps, bool io16) {
-  int rc = flow_resources(b);
-  if (rc) return rc;
+  HIP_TRY(b->sync.ensure(b->S, b->stream));
   const size_t per = (size_t)b->S * b->block / (io16 ? 2 : 1);
-  int maxm = kFlowMaxSteps;
+  int maxm = kHandoffMaxSteps;
   if (const char* e = getenv("ASP_NS_FLOW_MAX")) {  // tuning: frame steps per launch
     const int v = atoi(e);
-    if (v >= 2 && v <= kFlowMaxSteps) maxm = v;
+    if (v >= 2 && v <= kHandoffMaxSteps) maxm = v;
   }
   for (int k = 0; k < steps; k += maxm) {
     const int m = steps - k < maxm ? steps - k : maxm;
     if (b->kernel == 2)
-      HIP_TRY(launch_ns_frame2_flow(io16, b->state, b->hist, b->tables, din, dout, b->S, b->stream, b->flow_seq,
-                                    b->flow_abort, b->flow_count, m, k % ring, ring, per, b->flow_stamps));
+      HIP_TRY(launch_ns_frame2_flow(io16, b->state, b->hist, b->tables, din, dout, b->S, b->stream, b->sync.seq,
+                                    b->sync.abort, b->sync.count, m, k % ring, ring, per, b->flow_stamps));
     else
-      HIP_TRY(launch_ns_frame1_flow(io16, b->state, b->hist, b->tables, din, dout, b->S, b->stream, b->flow_seq,
-                                    b->flow_abort, b->flow_count, m, k % ring, ring, per, b->flow_stamps));
-    b->flow_count += (unsigned)m;
+      HIP_TRY(launch_ns_frame1_flow(io16, b->state, b->hist, b->tables, din, dout, b->S, b->stream, b->sync.seq,
+                                    b->sync.abort, b->sync.count, m, k % ring, ring, per, b->flow_stamps));
+    b->sync.enqueued(m);
   }
-  b->flow_unchecked = true;
   return ASP_OK;
 }
 
-// After the batch's stream has been synchronised: did a hand-off wait time out?  (It cannot while the
-// launches of one batch run as enqueued; a timeout means steps were skipped, so the call fails loudly and
-// the counters are put back in step.)
+// After the batch's stream has been synchronised: did a hand-off wait time out?  (HandoffSync::check)
 static int flow_check(AspNsBatch* b) {
-  if (!b->flow_unchecked) return ASP_OK;
-  b->flow_unchecked = false;
-  unsigned a = 0;
-  HIP_TRY(hipMemcpy(&a, b->flow_abort, sizeof a, hipMemcpyDeviceToHost));
-  if (a == 0) return ASP_OK;
-  std::vector<unsigned> seq((size_t)b->S, b->flow_count);
-  HIP_TRY(hipMemcpy(b->flow_seq, seq.data(), seq.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(b->flow_abort, 0, 16));
+  bool timed_out = false;
+  HIP_TRY(b->sync.check(b->S, &timed_out));
+  if (!timed_out) return ASP_OK;
   return fail(ASP_ERR_HIP, "NS hand-off wait timed out: frame steps were skipped, re-initialise the batch");
 }
 
@@ -1390,7 +1361,7 @@ int AspNsBatch_DebugFlowStamps(AspNsBatch* b, const float* in_dev, float* out_de
   DeviceScope dev_scope_;
   int rc = check(b);
   if (rc) return rc;
-  if (!in_dev || !out_dev || !stamps17 || steps < 2 || steps > kFlowMaxSteps || !flow_applies(b, steps))
+  if (!in_dev || !out_dev || !stamps17 || steps < 2 || steps > kHandoffMaxSteps || !flow_applies(b, steps))
     return fail(ASP_ERR_PARAM, "DebugFlowStamps: bad argument (hand-off build, 2..64 steps)");
   unsigned long long* d = nullptr;
   HIP_TRY(hipMalloc((void**)&d, 17 * sizeof(unsigned long long)));
@@ -1452,7 +1423,7 @@ int AspNsBatch_SetFlow(AspNsBatch* b, int mode) {
 // ahead of the device's.
 int AspNsBatch_DebugFlowDesync(AspNsBatch* b) {
   if (!b) return fail(ASP_ERR_PARAM, "null batch handle");
-  b->flow_count++;
+  b->sync.count++;
   return ASP_OK;
 }
 

@@ -22,11 +22,13 @@
 //     ASP_NS_REDUCE_TREE64P and the tests compare bit for bit (outputs and every state array).
 #include <hip/hip_runtime.h>
 
+#include "handoff.h"
 #include "ns_device.h"
 #include "ns_layout.h"
 #include "ns_pair_fft.h"
 
 namespace {
+using namespace asphandoff;
 using namespace aspns_dev;
 using namespace aspns_pair;
 
@@ -39,38 +41,16 @@ __device__ __forceinline__ unsigned long long ns_cu_tag() {
 
 constexpr int NS3 = 3;  // 2 owned bins + the tail bin 128
 
-// ---- the hand-off build (FLOW): consecutive frame steps overlap on the chip.
-// One launch carries M consecutive frame steps of the whole batch: blockIdx.y is the step, blockIdx.x the
-// group of four streams.  Workgroups are dispatched in linear order (x fastest), so every workgroup of
-// step j has been dispatched before the first one of step j + 1: the wave that takes stream s in step
-// j + 1 may therefore WAIT for the wave that has stream s in step j -- that wave is resident or done,
-// whatever else runs on the chip (the argument of a decoupled look-back scan).  What orders the two is a
-// word in memory: the wave that has finished stream s of step k stores seq[s] = k + 1 after draining its
-// stores; the wave that takes stream s in step k + 1 polls seq[s] before its first state load.  Every
-// state access of this build is an sc1 access (write-through stores, loads that bypass the CU's L1), the
-// form MI355X_MICROARCH.md's visibility section lists for hand-offs without an agent-scope fence per wave;
-// `in` / `out` frames and the constant tables are not handed off and stay plain.  The state still goes
-// through memory every step (SURVEY 8(d)'s frame-synchronous model: nothing of a stream stays on chip
-// between its steps); what disappears is the chip-wide phase lock of one launch per step (all waves load,
-// then all compute, then all store) and the idle time at every launch boundary.  The x extent of the grid
-// is a multiple of 8, so that (with workgroups dealt round-robin to the 8 XCDs) the two workgroups of a
-// stream's consecutive steps come from the same XCD's in-order share of the grid.  The wait is bounded
-// all the same: a wave that gives up sets the abort word, which every later wait sees, and the host
-// reports the failure (ns_api.hip, flow_check).
+// ---- the hand-off build (FLOW): consecutive frame steps overlap on the chip (the protocol: handoff.h).
+// What a stream's steps hand each other is its state block: every state access of this build is sc1; `in` /
+// `out` frames and the constant tables stay plain.  Step j of a launch reads / writes ring slot (slot0 + j) % ring.
 struct NsFlowArgs {
-  unsigned* seq;      // [num_streams]: number of hand-off steps stream s has completed
-  unsigned* abort_w;  // != 0: a wait timed out (1 + stream)
+  HandoffArgs hand;
   unsigned want;      // blockIdx.y == 0 processes step `want` of every stream
   int slot0;          // ring slot of that step; step j of the launch uses slot (slot0 + j) % ring
   int ring;
   unsigned per;       // floats between two ring slots of `in` / `out`
 };
-typedef __attribute__((address_space(1))) unsigned gu32;
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-constexpr int kSc1 = 16;  // cache-policy operand of the buffer intrinsics: sc1
 
 // One stream's state block: `uni` is a wave-uniform dword offset, `vec` the lane's dword offset.
 template <bool FLOW>
@@ -81,71 +61,30 @@ struct StateAcc {
     if constexpr (FLOW) rs = __builtin_amdgcn_make_buffer_rsrc(p, 0, aspns::kStreamDwords * 4, 0x00020000);
   }
   __device__ __forceinline__ float ld1(int uni, int vec) const {
-    if constexpr (FLOW) return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vec * 4, uni * 4, kSc1));
+    if constexpr (FLOW) return sc1_load1(rs, vec * 4, uni * 4);
     else return st[uni + vec];
   }
   __device__ __forceinline__ float2 ld2(int uni, int vec) const {
-    if constexpr (FLOW) {
-      const f32x2v v = __builtin_bit_cast(f32x2v, __builtin_amdgcn_raw_buffer_load_b64(rs, vec * 4, uni * 4, kSc1));
-      return make_float2(v.x, v.y);
-    } else {
-      return *reinterpret_cast<const float2*>(st + uni + vec);
-    }
+    if constexpr (FLOW) return sc1_load2(rs, vec * 4, uni * 4);
+    else return *reinterpret_cast<const float2*>(st + uni + vec);
   }
   __device__ __forceinline__ float4 ld4(int uni, int vec) const {
-    if constexpr (FLOW) {
-      const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, vec * 4, uni * 4, kSc1));
-      return make_float4(v.x, v.y, v.z, v.w);
-    } else {
-      return *reinterpret_cast<const float4*>(st + uni + vec);
-    }
+    if constexpr (FLOW) return sc1_load4(rs, vec * 4, uni * 4);
+    else return *reinterpret_cast<const float4*>(st + uni + vec);
   }
   __device__ __forceinline__ void st1(int uni, int vec, float v) const {
-    if constexpr (FLOW) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, vec * 4, uni * 4, kSc1);
+    if constexpr (FLOW) sc1_store1(rs, vec * 4, uni * 4, v);
     else st[uni + vec] = v;
   }
   __device__ __forceinline__ void st2(int uni, int vec, float a, float b) const {
-    if constexpr (FLOW) {
-      const f32x2v v = {a, b};
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, v), rs, vec * 4, uni * 4, kSc1);
-    } else {
-      *reinterpret_cast<float2*>(st + uni + vec) = make_float2(a, b);
-    }
+    if constexpr (FLOW) sc1_store2(rs, vec * 4, uni * 4, a, b);
+    else *reinterpret_cast<float2*>(st + uni + vec) = make_float2(a, b);
   }
   __device__ __forceinline__ void st4(int uni, int vec, float4 x) const {
-    if constexpr (FLOW) {
-      const f32x4v v = {x.x, x.y, x.z, x.w};
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), rs, vec * 4, uni * 4, kSc1);
-    } else {
-      *reinterpret_cast<float4*>(st + uni + vec) = x;
-    }
+    if constexpr (FLOW) sc1_store4(rs, vec * 4, uni * 4, x);
+    else *reinterpret_cast<float4*>(st + uni + vec) = x;
   }
 };
-
-// Wait until stream `stream` has completed `want` hand-off steps.  Returns false when the wait was given
-// up (the abort word is set: by this wave after ~0.1 s of polling, or by another one before).
-__device__ __forceinline__ bool flow_wait(const NsFlowArgs& fa, unsigned want, int stream, int lane) {
-  const gu32* f = (const gu32*)(fa.seq + stream);
-  unsigned spins = 0;
-  for (;;) {
-    const unsigned v = __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((unsigned)__builtin_amdgcn_readfirstlane((int)v) == want) break;
-    ++spins;
-    if ((spins & 63u) == 0u) {
-      const unsigned a = __hip_atomic_load((const gu32*)fa.abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__builtin_amdgcn_readfirstlane((int)a) != 0) return false;
-    }
-    if (spins > (1u << 17)) {
-      if (lane == 0) __hip_atomic_store((gu32*)fa.abort_w, 1u + (unsigned)stream, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-    __builtin_amdgcn_s_sleep(2);
-  }
-  // no instruction: keeps the compiler from moving the state loads above the poll
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  return true;
-}
-
 
 template <bool IO16, bool FLOW>
 __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ state,
@@ -249,7 +188,7 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
       const short4 a = *reinterpret_cast<const short4*>(in16);
       s4in = make_float4((float)a.x, (float)a.y, (float)a.z, (float)a.w);
     }
-    if (wave_live) wave_live = flow_wait(fa, flow_want, stream, lane);
+    if (wave_live) wave_live = handoff_wait(fa.hand, flow_want, stream, lane);
     sv = sa.ld1(kOffScalars, lane);
     const float4 ha = sa.ld4(kOffAnaHist, 4 * (lane < 24 ? lane : 23));
     const bool hsel = lane < 24;
@@ -306,11 +245,9 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
   // the step is done for this stream: the hand-off build publishes it, every store of this wave drained first
 #define NS_STREAM_DONE()                                                                       \
   if constexpr (FLOW) {                                                                        \
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                           \
+    handoff_drain();                                                                           \
     NS_STAMP(16)                                                                               \
-    if (lane == 0)                                                                             \
-      __hip_atomic_store((gu32*)(fa.seq + stream), flow_want + 1u, __ATOMIC_RELAXED,           \
-                         __HIP_MEMORY_SCOPE_AGENT);                                            \
+    if (lane == 0) handoff_publish(fa.hand.seq + stream, flow_want);                           \
   }                                                                                            \
   return;
 
@@ -921,7 +858,7 @@ hipError_t launch_ns_frame1(bool io16, float* state, int32_t* hist, const NsTabl
                             const float* in, float* out, int num_streams, hipStream_t s,
                             unsigned long long* stamps, int stamp_mode) {
   const dim3 grid((num_streams + 3) / 4), block(256);
-  const NsFlowArgs none = {nullptr, nullptr, 0u, 0, 1, 0u};
+  const NsFlowArgs none = {{nullptr, nullptr}, 0u, 0, 1, 0u};
   if (io16)
     hipLaunchKernelGGL((ns_frame1_kernel<true, false>), grid, block, 0, s, state, hist, T, in, out,
                        num_streams, stamps, stamp_mode, none);
@@ -940,7 +877,7 @@ hipError_t launch_ns_frame1_flow(bool io16, float* state, int32_t* hist, const N
                                  size_t per, unsigned long long* stamps) {
   const int gx = ((num_streams + 3) / 4 + 7) / 8 * 8;
   const dim3 grid(gx, steps), block(256);
-  const NsFlowArgs fa = {seq, abort_w, want, slot0, ring, (unsigned)per};
+  const NsFlowArgs fa = {{seq, abort_w}, want, slot0, ring, (unsigned)per};
   if (io16)
     hipLaunchKernelGGL((ns_frame1_kernel<true, true>), grid, block, 0, s, state, hist, T, in, out,
                        num_streams, stamps, 0, fa);

@@ -23,10 +23,12 @@
 // Needs an even stream count (the host sends an odd last stream to the one-stream kernel).
 #include <hip/hip_runtime.h>
 
+#include "handoff.h"
 #include "ns_device.h"
 #include "ns_layout.h"
 
 namespace {
+using namespace asphandoff;
 using namespace aspns_dev;
 
 constexpr int NS5 = 5;  // 4 owned bins + the tail bin 128
@@ -186,25 +188,16 @@ __device__ __forceinline__ float sat16f(float x) {
 }
 
 // --------------------------------------------------------------------------
-// The hand-off build (FLOW), as in ns_kernels1.hip: one launch carries M consecutive frame steps of the whole
-// batch (blockIdx.y = step), workgroups are dispatched in grid order, and a per-stream step counter in memory
-// orders step k + 1 of a stream behind its own step k.  Every state access is sc1 through ONE buffer resource over
-// the batch's state array (the two halves of a wave work on two streams, so the stream's offset is part of the
-// lane's offset); frames in / out and the tables stay plain.
+// The hand-off build (FLOW; the protocol: handoff.h): what a stream's steps hand each other is its state block, and
+// every state access is sc1 through ONE buffer resource over the batch's state array (the two halves of a wave work
+// on two streams, so the stream's offset is part of the lane's offset); frames in / out and the tables stay plain.
 struct NsFlowArgs2 {
-  unsigned* seq;      // [num_streams]: hand-off steps stream s has completed
-  unsigned* abort_w;  // != 0: a wait timed out (1 + stream)
+  HandoffArgs hand;
   unsigned want;      // blockIdx.y == 0 processes step `want` of every stream
   int slot0;          // ring slot of that step; step j of the launch uses slot (slot0 + j) % ring
   int ring;
   unsigned per;       // floats between two ring slots of `in` / `out`
 };
-typedef __attribute__((address_space(1))) unsigned gu32;
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-constexpr int kSc1 = 16;
 
 // The lane's stream: `uni` is a wave-uniform dword offset inside the stream's block, `vec` the lane's.
 template <bool FLOW>
@@ -220,69 +213,30 @@ struct StateAcc2 {
     }
   }
   __device__ __forceinline__ float ld1(int uni, int vec) const {
-    if constexpr (FLOW) return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, sb + vec * 4, uni * 4, kSc1));
+    if constexpr (FLOW) return sc1_load1(rs, sb + vec * 4, uni * 4);
     else return st[uni + vec];
   }
   __device__ __forceinline__ float2 ld2(int uni, int vec) const {
-    if constexpr (FLOW) {
-      const f32x2v v = __builtin_bit_cast(f32x2v, __builtin_amdgcn_raw_buffer_load_b64(rs, sb + vec * 4, uni * 4, kSc1));
-      return make_float2(v.x, v.y);
-    } else {
-      return *reinterpret_cast<const float2*>(st + uni + vec);
-    }
+    if constexpr (FLOW) return sc1_load2(rs, sb + vec * 4, uni * 4);
+    else return *reinterpret_cast<const float2*>(st + uni + vec);
   }
   __device__ __forceinline__ float4 ld4(int uni, int vec) const {
-    if constexpr (FLOW) {
-      const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rs, sb + vec * 4, uni * 4, kSc1));
-      return make_float4(v.x, v.y, v.z, v.w);
-    } else {
-      return *reinterpret_cast<const float4*>(st + uni + vec);
-    }
+    if constexpr (FLOW) return sc1_load4(rs, sb + vec * 4, uni * 4);
+    else return *reinterpret_cast<const float4*>(st + uni + vec);
   }
   __device__ __forceinline__ void st1(int uni, int vec, float v) const {
-    if constexpr (FLOW) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, sb + vec * 4, uni * 4, kSc1);
+    if constexpr (FLOW) sc1_store1(rs, sb + vec * 4, uni * 4, v);
     else st[uni + vec] = v;
   }
   __device__ __forceinline__ void st2(int uni, int vec, float a, float b) const {
-    if constexpr (FLOW) {
-      const f32x2v v = {a, b};
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, v), rs, sb + vec * 4, uni * 4, kSc1);
-    } else {
-      *reinterpret_cast<float2*>(st + uni + vec) = make_float2(a, b);
-    }
+    if constexpr (FLOW) sc1_store2(rs, sb + vec * 4, uni * 4, a, b);
+    else *reinterpret_cast<float2*>(st + uni + vec) = make_float2(a, b);
   }
   __device__ __forceinline__ void st4(int uni, int vec, float4 x) const {
-    if constexpr (FLOW) {
-      const f32x4v v = {x.x, x.y, x.z, x.w};
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), rs, sb + vec * 4, uni * 4, kSc1);
-    } else {
-      *reinterpret_cast<float4*>(st + uni + vec) = x;
-    }
+    if constexpr (FLOW) sc1_store4(rs, sb + vec * 4, uni * 4, x);
+    else *reinterpret_cast<float4*>(st + uni + vec) = x;
   }
 };
-
-// Wait until both streams of the wave (lanes 0-31: `stream` of the low half, 32-63: of the high half; a half past the
-// batch's last stream has `mine` false) have completed `want` hand-off steps.  False: given up (abort word set).
-__device__ __forceinline__ bool flow_wait2(const NsFlowArgs2& fa, unsigned want, int stream, bool mine, int lane) {
-  const gu32* f = (const gu32*)(fa.seq + stream);
-  unsigned spins = 0;
-  for (;;) {
-    const unsigned v = __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (__all(v == want || !mine)) break;
-    ++spins;
-    if ((spins & 63u) == 0u) {
-      const unsigned a = __hip_atomic_load((const gu32*)fa.abort_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__builtin_amdgcn_readfirstlane((int)a) != 0) return false;
-    }
-    if (spins > (1u << 17)) {
-      if (lane == 0) __hip_atomic_store((gu32*)fa.abort_w, 1u + (unsigned)stream, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-    __builtin_amdgcn_s_sleep(2);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the state loads below the poll
-  return true;
-}
 
 // launch bounds (256, 3): at most 168 VGPRs, three waves (six streams) per SIMD
 template <bool IO16, bool FLOW>
@@ -375,7 +329,8 @@ __global__ __launch_bounds__(256, 3) void ns_frame2_kernel(float* __restrict__ s
         i8[4] = (float)b.x; i8[5] = (float)b.y; i8[6] = (float)b.z; i8[7] = (float)b.w;
       }
     }
-    if (pair_live) flow_ok = flow_wait2(fa, flow_want, stream, mine, lane);
+    // both streams of the wave: each half polls its own stream's word (a half past the last stream has `mine` false)
+    if (pair_live) flow_ok = handoff_wait_lanes(fa.hand, flow_want, stream, mine, (unsigned)stream, lane);
     sv0 = sa.ld1(kOffScalars, lam);
     sv1 = sa.ld1(kOffScalars + 32, lam);
     const int lh = lam < 12 ? lam : 11;
@@ -1031,9 +986,8 @@ __global__ __launch_bounds__(256, 3) void ns_frame2_kernel(float* __restrict__ s
   }
   NS_STAMP(15)
   if constexpr (FLOW) {  // publish both streams' step: every store of this wave drained first
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lam == 0 && mine)
-      __hip_atomic_store((gu32*)(fa.seq + stream), flow_want + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    handoff_drain();
+    if (lam == 0 && mine) handoff_publish(fa.hand.seq + stream, flow_want);
   }
 #undef NS_STAMP
 #undef SCF
@@ -1054,7 +1008,7 @@ hipError_t launch_ns_frame2(bool io16, float* state, int32_t* hist, const NsTabl
                             unsigned long long* stamps) {
   // two streams per wave, eight per 256-thread workgroup; an odd count leaves the last wave's high half idle
   const dim3 grid(((num_streams + 1) / 2 + 3) / 4), block(256);
-  const NsFlowArgs2 none = {nullptr, nullptr, 0u, 0, 1, 0u};
+  const NsFlowArgs2 none = {{nullptr, nullptr}, 0u, 0, 1, 0u};
   if (io16)
     hipLaunchKernelGGL((ns_frame2_kernel<true, false>), grid, block, 0, s, state, hist, T, in, out,
                        num_streams, stamps, none);
@@ -1069,9 +1023,9 @@ hipError_t launch_ns_frame2_flow(bool io16, float* state, int32_t* hist, const N
                                  const float* in, float* out, int num_streams, hipStream_t s,
                                  unsigned* seq, unsigned* abort_w, unsigned want, int steps, int slot0, int ring,
                                  size_t per, unsigned long long* stamps) {
-  const int gx = (((num_streams + 1) / 2 + 3) / 4 + 7) / 8 * 8;  // a multiple of 8: see NsFlowArgs of ns_kernels1.hip
+  const int gx = (((num_streams + 1) / 2 + 3) / 4 + 7) / 8 * 8;  // a multiple of 8: see handoff.h
   const dim3 grid(gx, steps), block(256);
-  const NsFlowArgs2 fa = {seq, abort_w, want, slot0, ring, (unsigned)per};
+  const NsFlowArgs2 fa = {{seq, abort_w}, want, slot0, ring, (unsigned)per};
   if (io16)
     hipLaunchKernelGGL((ns_frame2_kernel<true, true>), grid, block, 0, s, state, hist, T, in, out,
                        num_streams, stamps, fa);

@@ -12,7 +12,7 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.environ.get("ASP_AMD_LIB") or os.path.join(LIBDIR, "libasp_amd.so")
 SOURCES = ["ns_kernels.hip", "ns_kernels1.hip", "ns_kernels2.hip", "ns_kernels_hb.hip", "ns_api.hip", "bt_kernels.hip", "bt_kernels8.hip", "bt_api.hip",
            "aec_kernels.hip", "aec_delay_kernels.hip", "aec_api.hip", "qmf_kernels.hip", "qmf_api.hip", "sinc_kernels.hip", "sinc_api.hip",
-           "vad_kernels.hip", "vad_api.hip"]
+           "vad_kernels.hip", "vad_api.hip", "aecm_kernels.hip", "aecm_api.hip"]
 C_SOURCES = ["wav_io.c"]  # host-only C (kept C, as in the reference)
 # -ffp-contract=off: parity with the reference depends on unfused mul/add.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",
@@ -27,7 +27,9 @@ _PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=8"]
 EXTRA = {"ns_kernels.hip": list(_PRELOAD), "ns_kernels1.hip": list(_PRELOAD), "ns_kernels2.hip": list(_PRELOAD),
          # the echo canceller's block is long straight-line code at 4 waves per SIMD: the compiler's ILP-first
          # scheduling measured 92.7-93.8 us per step against 95.5 us in one session (max-ilp: 97-99 us)
-         "aec_kernels.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]}
+         "aec_kernels.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
+         # the echo canceller's per-lane code: unrolled, its 65-bin loops spill to scratch (564 B); rolled, none
+         "aecm_kernels.hip": ["-fno-unroll-loops"]}
 # second builds of a source under another object name: (source, object, extra flags)
 VARIANTS = []
 for _item in filter(None, os.environ.get("ASP_HIPCC_EXTRA", "").split(";")):
@@ -53,9 +55,9 @@ def build_library(force=False, verbose=False):
     """Compile csrc/*.hip into lib/libasp_amd.so; returns its path."""
     os.makedirs(LIBDIR, exist_ok=True)
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC, "ns_layout.h"), os.path.join(CSRC, "ns_device.h"), os.path.join(CSRC, "ns_pair_fft.h"), os.path.join(CSRC, "bt_layout.h"), os.path.join(CSRC, "pk_f32.h"), os.path.join(CSRC, "bt_sure.h"), os.path.join(CSRC, "aec_layout.h"), os.path.join(CSRC, "aec_binspec.h"), os.path.join(CSRC, "aec_estimator.h"), os.path.join(CSRC, "sinc_layout.h"), os.path.join(CSRC, "device_scope.h"), os.path.join(CSRC, "handoff.h"), os.path.join(CSRC, "handoff_host.h"), os.path.join(CSRC, "vad_layout.h"),
+    hdrs = [os.path.join(CSRC, "ns_layout.h"), os.path.join(CSRC, "ns_device.h"), os.path.join(CSRC, "ns_pair_fft.h"), os.path.join(CSRC, "bt_layout.h"), os.path.join(CSRC, "pk_f32.h"), os.path.join(CSRC, "bt_sure.h"), os.path.join(CSRC, "aec_layout.h"), os.path.join(CSRC, "aec_binspec.h"), os.path.join(CSRC, "aec_estimator.h"), os.path.join(CSRC, "sinc_layout.h"), os.path.join(CSRC, "device_scope.h"), os.path.join(CSRC, "handoff.h"), os.path.join(CSRC, "handoff_host.h"), os.path.join(CSRC, "vad_layout.h"), os.path.join(CSRC, "aecm_layout.h"), os.path.join(CSRC, "aecm_core.h"),
                    os.path.join(ROOT, "include", "asp_ns.h"), os.path.join(ROOT, "include", "asp_bt.h"), os.path.join(ROOT, "include", "asp_aec.h"), os.path.join(ROOT, "include", "asp_split.h"), os.path.join(ROOT, "include", "asp_resample.h"),
-                   os.path.join(ROOT, "include", "asp_vad.h")]
+                   os.path.join(ROOT, "include", "asp_vad.h"), os.path.join(ROOT, "include", "asp_aecm.h")]
     objs = []
     inc = ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
     for s in srcs:
@@ -84,6 +86,14 @@ def build_library(force=False, verbose=False):
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)
         objs.append(o)
+    # the CPU build of the echo canceller's core, for the tests only (no CPU path in libasp_amd.so)
+    src = os.path.join(CSRC, "aecm_restate.cpp")
+    so = os.path.join(LIBDIR, "libaecm_restate.so")
+    if force or _stale(so, [src] + hdrs):
+        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall"] + inc + [src, "-o", so]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
     if force or _stale(LIB, objs):
         cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB]
         if verbose:
@@ -97,7 +107,7 @@ def build_drivers(verbose=False):
     out_dir = os.path.join(ROOT, "drivers", "bin")
     os.makedirs(out_dir, exist_ok=True)
     built = []
-    for name in ["test_ns_module", "ns_batch_wav", "test_aec_module", "bt_main", "test_vad_module"]:
+    for name in ["test_ns_module", "ns_batch_wav", "test_aec_module", "bt_main", "test_aecm_module", "test_vad_module"]:
         src = os.path.join(ROOT, "drivers", name + ".c")
         exe = os.path.join(out_dir, name)
         if _stale(exe, [src, LIB]):

@@ -136,3 +136,47 @@ def vad_frames(num_streams, num_frames, fs, frame_ms, seed=0, stream0=0, frame0=
     x = np.where(hush, (n >> 15), x)
     x = np.clip(x, -32768, 32767).astype(np.int16)
     return np.ascontiguousarray(x.reshape(num_streams, num_frames, L).transpose(1, 0, 2))
+
+
+def aecm_pair(num_streams, num_frames, n, delay=40, seed=0, stream0=0):
+    """AECM input, three int16 arrays [num_frames][num_streams][n]: far, near, clean.  Integer only.
+
+    Far: a talker (triangle of period 57 + 7 (s mod 5) samples plus noise, amplitude 2000..7000) while
+    ((b + 13 s) mod 90) < 55 (b: absolute 80-sample block), else a noise floor.  Near: far delayed by
+    `delay` + (s mod 7) samples through the echo path (x[t] / 2 - x[t - 3] / 8 + x[t - 9] / 16), plus
+    near-end talk (a second triangle) while ((b + 29 s) mod 150) >= 120 -- the double-talk segments --
+    plus noise.  Clean: near without its noise.
+    """
+    L = n * num_frames
+    s = np.arange(stream0, stream0 + num_streams, dtype=np.int64)
+    seeds = ((777 + 104729 * (s + 1000003 * seed)) & 0xFFFFFFFF).astype(np.uint32)
+    pad = delay + 6 + 9
+    u = _lcg_u32(seeds, 0, L + pad).astype(np.int64)
+    nz = (u >> 16) - 32768
+    t = np.arange(-pad, L, dtype=np.int64)[None, :]
+    b = np.maximum(t, 0) // 80
+    period = (57 + 7 * (s % 5))[:, None]
+    tri = np.abs(2 * 65536 * (t % period) // period - 65536) - 32768
+    amp = 2000 + ((b * 29 + 5 * s[:, None]) % 11) * 500
+    talk = ((b + 13 * s[:, None]) % 90) < 55
+    far = np.where(talk, (tri * amp) // 32768 + (nz * (amp // 8)) // 32768, (nz * 40) // 32768)
+    far = np.where(t < 0, 0, far)
+    d = delay + (s % 7)
+    idx = np.arange(L)[None, :] + pad
+    g = lambda k: np.take_along_axis(far, idx - d[:, None] - k, axis=1)
+    echo = g(0) // 2 - g(3) // 8 + g(9) // 16
+    tn = np.arange(L, dtype=np.int64)[None, :]
+    bn = tn // 80
+    period2 = (41 + 5 * (s % 3))[:, None]
+    tri2 = np.abs(2 * 65536 * (tn % period2) // period2 - 65536) - 32768
+    dt = ((bn + 29 * s[:, None]) % 150) >= 120
+    clean = echo + np.where(dt, (tri2 * 3000) // 32768, 0)
+    noise = (nz[:, pad:] * 60) // 32768
+    near = clean + noise
+    far = far[:, pad:]
+
+    def shape(x):
+        x = np.clip(x, -32768, 32767).astype(np.int16)
+        return np.ascontiguousarray(x.reshape(num_streams, num_frames, n).transpose(1, 0, 2))
+
+    return shape(far), shape(near), shape(clean)

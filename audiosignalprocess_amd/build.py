@@ -12,7 +12,7 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.environ.get("ASP_AMD_LIB") or os.path.join(LIBDIR, "libasp_amd.so")
 SOURCES = ["ns_kernels.hip", "ns_kernels1.hip", "ns_kernels2.hip", "ns_kernels_hb.hip", "ns_api.hip", "bt_kernels.hip", "bt_kernels8.hip", "bt_api.hip",
            "aec_kernels.hip", "aec_delay_kernels.hip", "aec_api.hip", "qmf_kernels.hip", "qmf_api.hip", "sinc_kernels.hip", "sinc_api.hip",
-           "vad_kernels.hip", "vad_api.hip", "aecm_kernels.hip", "aecm_api.hip"]
+           "vad_kernels.hip", "vad_api.hip", "aecm_kernels.hip", "aecm_api.hip", "nsx_kernels.hip", "nsx_api.hip"]
 C_SOURCES = ["wav_io.c"]  # host-only C (kept C, as in the reference)
 # -ffp-contract=off: parity with the reference depends on unfused mul/add.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",
@@ -55,9 +55,9 @@ def build_library(force=False, verbose=False):
     """Compile csrc/*.hip into lib/libasp_amd.so; returns its path."""
     os.makedirs(LIBDIR, exist_ok=True)
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC, "ns_layout.h"), os.path.join(CSRC, "ns_device.h"), os.path.join(CSRC, "ns_pair_fft.h"), os.path.join(CSRC, "bt_layout.h"), os.path.join(CSRC, "pk_f32.h"), os.path.join(CSRC, "bt_sure.h"), os.path.join(CSRC, "aec_layout.h"), os.path.join(CSRC, "aec_binspec.h"), os.path.join(CSRC, "aec_estimator.h"), os.path.join(CSRC, "sinc_layout.h"), os.path.join(CSRC, "device_scope.h"), os.path.join(CSRC, "handoff.h"), os.path.join(CSRC, "handoff_host.h"), os.path.join(CSRC, "vad_layout.h"), os.path.join(CSRC, "aecm_layout.h"), os.path.join(CSRC, "aecm_core.h"),
+    hdrs = [os.path.join(CSRC, "ns_layout.h"), os.path.join(CSRC, "ns_device.h"), os.path.join(CSRC, "ns_pair_fft.h"), os.path.join(CSRC, "bt_layout.h"), os.path.join(CSRC, "pk_f32.h"), os.path.join(CSRC, "bt_sure.h"), os.path.join(CSRC, "aec_layout.h"), os.path.join(CSRC, "aec_binspec.h"), os.path.join(CSRC, "aec_estimator.h"), os.path.join(CSRC, "sinc_layout.h"), os.path.join(CSRC, "device_scope.h"), os.path.join(CSRC, "handoff.h"), os.path.join(CSRC, "handoff_host.h"), os.path.join(CSRC, "vad_layout.h"), os.path.join(CSRC, "aecm_layout.h"), os.path.join(CSRC, "aecm_core.h"), os.path.join(CSRC, "nsx_layout.h"), os.path.join(CSRC, "nsx_core.h"),
                    os.path.join(ROOT, "include", "asp_ns.h"), os.path.join(ROOT, "include", "asp_bt.h"), os.path.join(ROOT, "include", "asp_aec.h"), os.path.join(ROOT, "include", "asp_split.h"), os.path.join(ROOT, "include", "asp_resample.h"),
-                   os.path.join(ROOT, "include", "asp_vad.h"), os.path.join(ROOT, "include", "asp_aecm.h")]
+                   os.path.join(ROOT, "include", "asp_vad.h"), os.path.join(ROOT, "include", "asp_aecm.h"), os.path.join(ROOT, "include", "asp_nsx.h")]
     objs = []
     inc = ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
     for s in srcs:
@@ -94,6 +94,14 @@ def build_library(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)
+    # likewise for the fixed-point noise suppressor's core
+    src = os.path.join(CSRC, "nsx_restate.cpp")
+    so = os.path.join(LIBDIR, "libnsx_restate.so")
+    if force or _stale(so, [src] + hdrs):
+        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall"] + inc + [src, "-o", so]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
     if force or _stale(LIB, objs):
         cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB]
         if verbose:
@@ -107,7 +115,7 @@ def build_drivers(verbose=False):
     out_dir = os.path.join(ROOT, "drivers", "bin")
     os.makedirs(out_dir, exist_ok=True)
     built = []
-    for name in ["test_ns_module", "ns_batch_wav", "test_aec_module", "bt_main", "test_aecm_module", "test_vad_module"]:
+    for name in ["test_ns_module", "ns_batch_wav", "test_aec_module", "bt_main", "test_aecm_module", "test_nsx_module", "test_vad_module"]:
         src = os.path.join(ROOT, "drivers", name + ".c")
         exe = os.path.join(out_dir, name)
         if _stale(exe, [src, LIB]):

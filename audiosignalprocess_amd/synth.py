@@ -180,3 +180,28 @@ def aecm_pair(num_streams, num_frames, n, delay=40, seed=0, stream0=0):
         return np.ascontiguousarray(x.reshape(num_streams, num_frames, n).transpose(1, 0, 2))
 
     return shape(far), shape(near), shape(clean)
+
+
+def nsx_frames(num_streams, num_frames, n, num_bands=1, seed=0, stream0=0, level=800):
+    """NSX input, int16 [num_frames][num_bands][num_streams][n].  Integer only, regenerable from its arguments.
+
+    Band 0: noise of amplitude `level` (from the LCG) plus speech-like bursts: a triangle of period
+    41 + 6 (s mod 5) samples, amplitude 3000..9000, on while ((f + 11 s) mod 70) < 30 (f: frame).
+    Higher bands: noise of amplitude level / 2 with a fainter copy of the bursts.
+    """
+    L = n * num_frames
+    s = np.arange(stream0, stream0 + num_streams, dtype=np.int64)
+    out = np.zeros((num_frames, num_bands, num_streams, n), np.int16)
+    t = np.arange(L, dtype=np.int64)[None, :]
+    f = t // n
+    period = (41 + 6 * (s % 5))[:, None]
+    tri = np.abs(2 * 65536 * (t % period) // period - 65536) - 32768
+    amp = 3000 + ((f * 17 + 3 * s[:, None]) % 13) * 500
+    on = ((f + 11 * s[:, None]) % 70) < 30
+    for b in range(num_bands):
+        seeds = ((4242 + 104729 * (s + 1000003 * seed) + 7919 * b) & 0xFFFFFFFF).astype(np.uint32)
+        nz = (_lcg_u32(seeds, 0, L).astype(np.int64) >> 16) - 32768
+        lev = level if b == 0 else level // 2
+        x = (nz * lev) // 32768 + np.where(on, (tri * amp) // 32768, 0) // (1 if b == 0 else 8 * b)
+        out[:, b] = np.clip(x, -32768, 32767).astype(np.int16).reshape(num_streams, num_frames, n).transpose(1, 0, 2)
+    return out

@@ -1,12 +1,11 @@
 """Python mirror of the batched echo-canceller C-ABI (include/asp_aec.h) over ctypes.
 Plumbing only -- every call goes into libasp_amd.so; no CPU fallback."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from ._abi import MEM_DEVICE, MEM_HOST, AecConfig, AspAecControl, AspAecState
-from .ns import AspError, load_library
+from .ns import AspError, _check, _declare, load_library
 
 _sig_done = False
 
@@ -50,19 +49,9 @@ def _lib():
             "AspAec_host_table": [ip, vp, ip],
             "AspAec_delay_estimator_batch": [vp, ip, vp, vp, ip, ip],
         }
-        for name, args in sig.items():
-            if os.environ.get("ASP_AMD_LIB") and not hasattr(lib, name):
-                continue  # an earlier build of the library loaded for a same-box A / B run (build.py)
-            fn = getattr(lib, name)
-            fn.argtypes = args
-            fn.restype = C.c_int
+        _declare(lib, sig)
         _sig_done = True
     return lib
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise AspError("%s failed (%d)" % (what, rc))
 
 
 class AecBatch:

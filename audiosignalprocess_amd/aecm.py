@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._abi import MEM_HOST
-from .ns import AspError, device_count, load_library as _load
+from .ns import AspError, _check, _declare, device_count, load_library as _load  # noqa: F401
 
 AECM_UNINITIALIZED_ERROR = 12002
 AECM_NULL_POINTER_ERROR = 12003
@@ -61,10 +61,7 @@ def load_library():
             "WebRtcAecm_GetEchoPath": [vp, vp, sz],
             "WebRtcAecm_get_error_code": [vp],
         }
-        for name, args in sig.items():
-            fn = getattr(lib, name)
-            fn.argtypes = args
-            fn.restype = C.c_int
+        _declare(lib, sig)
         lib.WebRtcAecm_echo_path_size_bytes.argtypes = []
         lib.WebRtcAecm_echo_path_size_bytes.restype = sz
         lib.AspAecm_state_size.argtypes = []
@@ -80,11 +77,6 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def _check(r, what):
-    if r != 0:
-        raise AspError("%s failed (%d)" % (what, r))
-
-
 class AecmBatch:
     """num_streams independent echo cancellers; host numpy buffers (ASP_MEM_HOST)."""
 
@@ -92,8 +84,7 @@ class AecmBatch:
         self.lib = load_library()
         self.S = num_streams
         h = C.c_void_p()
-        if self.lib.AspAecmBatch_Create(C.byref(h), num_streams, device) != 0:
-            raise RuntimeError("AspAecmBatch_Create failed (no HIP device?)")
+        _check(self.lib.AspAecmBatch_Create(C.byref(h), num_streams, device), "AspAecmBatch_Create")
         self.h = h
         if fs is not None:
             self.init(fs)

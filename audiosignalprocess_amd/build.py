@@ -1,5 +1,6 @@
 """In-tree build of the HIP library (hipcc, gfx950 only).  No JIT cache: the
 resulting audiosignalprocess_amd/lib/libasp_amd.so travels with the tree."""
+import glob
 import os
 import shutil
 import subprocess
@@ -55,9 +56,7 @@ def build_library(force=False, verbose=False):
     """Compile csrc/*.hip into lib/libasp_amd.so; returns its path."""
     os.makedirs(LIBDIR, exist_ok=True)
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC, "ns_layout.h"), os.path.join(CSRC, "ns_device.h"), os.path.join(CSRC, "ns_pair_fft.h"), os.path.join(CSRC, "bt_layout.h"), os.path.join(CSRC, "pk_f32.h"), os.path.join(CSRC, "bt_sure.h"), os.path.join(CSRC, "aec_layout.h"), os.path.join(CSRC, "aec_binspec.h"), os.path.join(CSRC, "aec_estimator.h"), os.path.join(CSRC, "sinc_layout.h"), os.path.join(CSRC, "device_scope.h"), os.path.join(CSRC, "handoff.h"), os.path.join(CSRC, "handoff_host.h"), os.path.join(CSRC, "vad_layout.h"), os.path.join(CSRC, "aecm_layout.h"), os.path.join(CSRC, "aecm_core.h"), os.path.join(CSRC, "nsx_layout.h"), os.path.join(CSRC, "nsx_core.h"),
-                   os.path.join(ROOT, "include", "asp_ns.h"), os.path.join(ROOT, "include", "asp_bt.h"), os.path.join(ROOT, "include", "asp_aec.h"), os.path.join(ROOT, "include", "asp_split.h"), os.path.join(ROOT, "include", "asp_resample.h"),
-                   os.path.join(ROOT, "include", "asp_vad.h"), os.path.join(ROOT, "include", "asp_aecm.h"), os.path.join(ROOT, "include", "asp_nsx.h")]
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(ROOT, "include", "*.h")))
     objs = []
     inc = ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
     for s in srcs:
@@ -86,22 +85,15 @@ def build_library(force=False, verbose=False):
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)
         objs.append(o)
-    # the CPU build of the echo canceller's core, for the tests only (no CPU path in libasp_amd.so)
-    src = os.path.join(CSRC, "aecm_restate.cpp")
-    so = os.path.join(LIBDIR, "libaecm_restate.so")
-    if force or _stale(so, [src] + hdrs):
-        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall"] + inc + [src, "-o", so]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.run(cmd, check=True)
-    # likewise for the fixed-point noise suppressor's core
-    src = os.path.join(CSRC, "nsx_restate.cpp")
-    so = os.path.join(LIBDIR, "libnsx_restate.so")
-    if force or _stale(so, [src] + hdrs):
-        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall"] + inc + [src, "-o", so]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.run(cmd, check=True)
+    # the CPU builds of the AECM and NSX cores, for the tests only (no CPU path in libasp_amd.so)
+    for src_name, so_name in (("aecm_restate.cpp", "libaecm_restate.so"), ("nsx_restate.cpp", "libnsx_restate.so")):
+        src = os.path.join(CSRC, src_name)
+        so = os.path.join(LIBDIR, so_name)
+        if force or _stale(so, [src] + hdrs):
+            cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall"] + inc + [src, "-o", so]
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.run(cmd, check=True)
     if force or _stale(LIB, objs):
         cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB]
         if verbose:

@@ -6,7 +6,7 @@
 // ProcOps); all sample and spectrum data stays in HBM.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include "device_scope.h"
+#include "api_common.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -57,20 +57,8 @@ hipError_t launch_aec_rdft128(const float* src, float* dst, int isgn, int count,
 
 namespace {
 
-thread_local char g_aec_err[512] = "";
-int aec_fail(int code, const char* what, hipError_t e = hipSuccess) {
-  if (e != hipSuccess)
-    snprintf(g_aec_err, sizeof g_aec_err, "%s: %s", what, hipGetErrorString(e));
-  else
-    snprintf(g_aec_err, sizeof g_aec_err, "%s", what);
-  fprintf(stderr, "asp_aec: %s\n", g_aec_err);
-  return code;
-}
-#define AEC_TRY(expr)                                             \
-  do {                                                            \
-    hipError_t e_ = (expr);                                       \
-    if (e_ != hipSuccess) return aec_fail(ASP_ERR_HIP, #expr, e_); \
-  } while (0)
+#define aec_fail(...) asp_fail("asp_aec", __VA_ARGS__)
+#define AEC_TRY(x) ASP_TRY("asp_aec", x)
 
 // ------------------------------------------------------------------ tables
 // NOTE: C++ translation unit; every libm call casts to double explicitly so the arithmetic is
@@ -519,9 +507,9 @@ void init_delay_state(AspAecDelayState* d, int lookahead, int allowed_offset) {
   d->previous_delay = -2;
   d->shift_offset = 5;  // kInitialShiftOffset, aec_core.c:102
 }
-int init_delay_device(AspAecBatch* b) {
+int init_delay_device(AspAecBatch* b, AspDeviceScope& dev_scope_) {
   std::vector<DelayBlock> all((size_t)b->S);
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   AEC_TRY(hipStreamSynchronize(b->stream));
   AEC_TRY(hipMemcpy(all.data(), b->dblocks, all.size() * sizeof(DelayBlock), hipMemcpyDeviceToHost));
   for (auto& d : all) {
@@ -534,7 +522,7 @@ int init_delay_device(AspAecBatch* b) {
 }
 
 // InitMetrics (aec_core.c:548-583) for every stream, ordered on the batch's stream.
-int init_metrics_device(AspAecBatch* b) {
+int init_metrics_device(AspAecBatch* b, AspDeviceScope& dev_scope_) {
   AspAecMetricsState m;
   memset(&m, 0, sizeof m);
   AspAecPowerLevel* lv[4] = {&m.farlevel, &m.nearlevel, &m.linoutlevel, &m.nlpoutlevel};
@@ -547,7 +535,7 @@ int init_metrics_device(AspAecBatch* b) {
   static_assert(sizeof(AspAecMetricsState) == 65 * 4 && sizeof(AspAecMetricsState) <= kMetDwords * 4, "metrics image");
   std::vector<float> all((size_t)b->S * kMetDwords, 0.f);
   for (int s = 0; s < b->S; ++s) memcpy(all.data() + (size_t)s * kMetDwords, &m, sizeof m);
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   AEC_TRY(hipStreamSynchronize(b->stream));
   AEC_TRY(hipMemcpy(b->metrics, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
   return 0;
@@ -1333,11 +1321,7 @@ int AspAecBatch_Create(AspAecBatch** out, int num_streams, int device) {
   AspDeviceScope dev_scope_;
   if (!out || num_streams <= 0) return aec_fail(ASP_ERR_PARAM, "AspAecBatch_Create: bad argument");
   *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return aec_fail(ASP_ERR_NO_DEVICE, "no HIP device: the echo canceller has no CPU fallback");
-  if (device < 0 || device >= count) return aec_fail(ASP_ERR_PARAM, "device ordinal out of range");
-  AEC_TRY(hipSetDevice(device));
+  if (int rc = dev_scope_.select("asp_aec", device, ASP_ERR_PARAM, "no HIP device: the echo canceller has no CPU fallback")) return rc;
   AspAecBatch* b = new AspAecBatch();
   b->S = num_streams;
   b->device = device;
@@ -1397,7 +1381,7 @@ int AspAecBatch_Free(AspAecBatch* b) {
     delete b;
     return 0;
   }
-  (void)hipSetDevice(b->device);
+  (void)dev_scope_.select(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->state) (void)hipFree(b->state);
   if (b->far_ring) (void)hipFree(b->far_ring);
@@ -1440,6 +1424,7 @@ int AspAecBatch_num_streams(const AspAecBatch* b) { return b ? b->S : 0; }
 int AspAecBatch_get_error_code(const AspAecBatch* b) { return b ? b->lastError : AEC_NULL_POINTER_ERROR; }
 
 int AspAecBatch_set_config(AspAecBatch* b, AecConfig config) {  // echo_cancellation.c:410-438
+  AspDeviceScope dev_scope_;
   if (!b) return aec_fail(ASP_ERR_PARAM, "null batch handle");
   if (b->initFlag != kInitCheck) {
     b->lastError = AEC_UNINITIALIZED_ERROR;
@@ -1471,12 +1456,12 @@ int AspAecBatch_set_config(AspAecBatch* b, AecConfig config) {  // echo_cancella
   b->nlp_mode = config.nlpMode;  // WebRtcAec_SetConfigCore, aec_core.c:1844-1862
   b->metricsMode = config.metricsMode;
   if (b->metricsMode && !b->sim) {
-    const int err = init_metrics_device(b);
+    const int err = init_metrics_device(b, dev_scope_);
     if (err) return err;
   }
   b->delay_logging = config.delay_logging;
   if (b->delay_logging && !b->sim) {  // memset(delay_histogram), aec_core.c:1858-1860
-    AEC_TRY(hipSetDevice(b->device));
+    AEC_TRY(dev_scope_.select(b->device));
     AEC_TRY(hipMemset2DAsync(reinterpret_cast<char*>(b->dblocks) + offsetof(DelayBlock, s.delay_histogram), sizeof(DelayBlock), 0,
                              sizeof(((AspAecDelayState*)nullptr)->delay_histogram), (size_t)b->S, b->stream));
   }
@@ -1564,7 +1549,7 @@ int AspAecBatch_Init(AspAecBatch* b, int32_t sampFreq, int32_t scSampFreq) {  //
   init_control(b, sampFreq, scSampFreq);
   memset(b->rs_skewData, 0, sizeof b->rs_skewData);
   if (!b->sim) {
-    AEC_TRY(hipSetDevice(b->device));
+    AEC_TRY(dev_scope_.select(b->device));
     AEC_TRY(hipStreamSynchronize(b->stream));
     if (old_num_part != kNumPartNormal) {  // back to the 12-partition blocks
       AEC_TRY(hipFree(b->state));
@@ -1582,9 +1567,9 @@ int AspAecBatch_Init(AspAecBatch* b, int32_t sampFreq, int32_t scSampFreq) {  //
     // on the batch's own (non-blocking) stream: a null-stream memset is not ordered with its kernels
     AEC_TRY(hipMemsetAsync(b->far_ring, 0, far_bytes(b), b->stream));  // WebRtc_InitBuffer zeroes the rings
     AEC_TRY(hipStreamSynchronize(b->stream));
-    const int err = init_metrics_device(b);  // aec_core.c:1612-1613
+    const int err = init_metrics_device(b, dev_scope_);  // aec_core.c:1612-1613
     if (err) return err;
-    const int err2 = init_delay_device(b);   // aec_core.c:1502-1516
+    const int err2 = init_delay_device(b, dev_scope_);   // aec_core.c:1502-1516
     if (err2) return err2;
     // WebRtcAec_InitResampler (echo_cancellation.c:221, aec_resampler.c:55-66)
     AEC_TRY(hipMemsetAsync(b->rs_buffer, 0, (size_t)b->S * kResamplerBufferSize * sizeof(float), b->stream));
@@ -1597,7 +1582,7 @@ int AspAecBatch_BufferFarend(AspAecBatch* b, const float* farend, int nrOfSample
   const int chk = check_running(b, farend, nrOfSamples);
   if (chk != 0) return chk;
   if (b->sim) return buffer_farend_device(b, farend, nrOfSamples);
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   const float* dev = farend;
   if (mem == ASP_MEM_HOST) {
     AEC_TRY(hipMemcpyAsync(b->stage_far, farend, (size_t)b->S * nrOfSamples * sizeof(float), hipMemcpyHostToDevice, b->stream));
@@ -1609,7 +1594,7 @@ int AspAecBatch_BufferFarend(AspAecBatch* b, const float* farend, int nrOfSample
   return 0;
 }
 
-static int process_impl(AspAecBatch* b, const float* nearend, const float* near_high, float* out,
+static int process_impl(AspAecBatch* b, AspDeviceScope& dev_scope_, const float* nearend, const float* near_high, float* out,
                         float* out_high, int nrOfSamples, int msInSndCardBuf, int mem, int32_t skew);
 
 int AspAecBatch_Process(AspAecBatch* b, const float* nearend, float* out, int nrOfSamples,
@@ -1619,7 +1604,7 @@ int AspAecBatch_Process(AspAecBatch* b, const float* nearend, float* out, int nr
     b->lastError = AEC_BAD_PARAMETER_ERROR;  // a 32 kHz batch needs both bands (ProcessBands)
     return -1;
   }
-  return process_impl(b, nearend, nullptr, out, nullptr, nrOfSamples, msInSndCardBuf, mem, skew);
+  return process_impl(b, dev_scope_, nearend, nullptr, out, nullptr, nrOfSamples, msInSndCardBuf, mem, skew);
 }
 
 int AspAecBatch_ProcessBands(AspAecBatch* b, const float* near_low, const float* near_high,
@@ -1630,7 +1615,7 @@ int AspAecBatch_ProcessBands(AspAecBatch* b, const float* near_low, const float*
     b->lastError = b->num_high < 1 ? AEC_BAD_PARAMETER_ERROR : AEC_NULL_POINTER_ERROR;
     return -1;
   }
-  return process_impl(b, near_low, near_high, out_low, out_high, nrOfSamples, msInSndCardBuf, mem, skew);
+  return process_impl(b, dev_scope_, near_low, near_high, out_low, out_high, nrOfSamples, msInSndCardBuf, mem, skew);
 }
 
 int AspAecBatch_num_bands(const AspAecBatch* b) { return b ? 1 + b->num_high : 0; }
@@ -1650,7 +1635,7 @@ int AspAecBatch_ProcessV(AspAecBatch* b, const float* nearend, float* out, int n
   if (chk != 0) return chk;
   if (!msInSndCardBuf) return aec_fail(ASP_ERR_PARAM, "ProcessV: null delay array");
   if (mem != ASP_MEM_HOST && mem != ASP_MEM_DEVICE) return aec_fail(ASP_ERR_PARAM, "mem must be ASP_MEM_HOST or ASP_MEM_DEVICE");
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   {
     const int rc = enter_vmode(b);
     if (rc != 0) return rc;
@@ -1686,7 +1671,7 @@ int AspAecBatch_InitStream(AspAecBatch* b, int stream) {
     return -1;
   }
   if (stream < 0 || stream >= b->S) return aec_fail(ASP_ERR_PARAM, "InitStream: stream out of range");
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   {
     const int rc = enter_vmode(b);
     if (rc != 0) return rc;
@@ -1722,7 +1707,7 @@ int AspAecBatch_GetControlStream(AspAecBatch* b, int stream, AspAecControl* c) {
   return ASP_OK;
 }
 
-static int process_impl(AspAecBatch* b, const float* nearend, const float* near_high, float* out,
+static int process_impl(AspAecBatch* b, AspDeviceScope& dev_scope_, const float* nearend, const float* near_high, float* out,
                         float* out_high, int nrOfSamples, int msInSndCardBuf, int mem, int32_t skew) {
   if (b && out == nullptr) {
     b->lastError = AEC_NULL_POINTER_ERROR;
@@ -1737,7 +1722,7 @@ static int process_impl(AspAecBatch* b, const float* nearend, const float* near_
     const int err_sim = process_device(b, nearend, out, nrOfSamples, msInSndCardBuf, &rc_sim, skew);
     return err_sim != 0 ? err_sim : rc_sim;
   }
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   const size_t bytes = (size_t)b->S * nrOfSamples * sizeof(float);
   const float* nd = nearend;
   float* od = out;
@@ -1786,7 +1771,7 @@ int AspAecBatch_Run(AspAecBatch* b, const float* farend, const float* nearend, f
   if (num_frames < 0) return aec_fail(ASP_ERR_PARAM, "Run: num_frames < 0");
   if (b->skewMode == kAecTrue)  // the skew estimate is a function of the calls' skew arguments: Process / ProcessBands carry one
     return aec_fail(ASP_ERR_STATE, "Run: no skew argument; with skew compensation on, feed the frames through BufferFarend / Process");
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   const size_t per = (size_t)b->S * nrOfSamples;
   int rc_all = 0;
   if (mem == ASP_MEM_HOST) {
@@ -1866,7 +1851,7 @@ int AspAecBatch_TimedSteps(AspAecBatch* b, const float* farend, const float* nea
   if (check_running(b, farend, nrOfSamples) != 0) return -1;
   if (b->skewMode == kAecTrue)
     return aec_fail(ASP_ERR_STATE, "TimedSteps: no skew argument; with skew compensation on, feed the frames through BufferFarend / Process");
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   const size_t per = (size_t)b->S * nrOfSamples;
   // two chains when the batch is large enough to fill the chip twice over and past its start-up phase
   // (whose pass-through copies stay on the main stream); ASP_AEC_CHAINS=1 keeps one
@@ -1917,7 +1902,7 @@ int AspAecBatch_Synchronize(AspAecBatch* b) {
   AspDeviceScope dev_scope_;
   if (b && b->sim) return aec_fail(ASP_ERR_STATE, "AspAecBatch_Synchronize: control-only handle");
   if (!b) return aec_fail(ASP_ERR_PARAM, "null batch handle");
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   AEC_TRY(hipStreamSynchronize(b->stream));
   return aec_flow_check(b);
 }
@@ -1933,7 +1918,7 @@ int AspAecBatch_ExportState(AspAecBatch* b, int stream, AspAecState* out) {
   AspDeviceScope dev_scope_;
   if (b && b->sim) return aec_fail(ASP_ERR_STATE, "AspAecBatch_ExportState: control-only handle");
   if (!b || !out || stream < 0 || stream >= b->S) return aec_fail(ASP_ERR_PARAM, "ExportState: bad argument");
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   AEC_TRY(hipStreamSynchronize(b->stream));
   const int kStateDwords = state_dwords(b);
   std::vector<float> blk(kStateDwords);
@@ -1947,7 +1932,7 @@ int AspAecBatch_ImportState(AspAecBatch* b, int stream, const AspAecState* in) {
   AspDeviceScope dev_scope_;
   if (b && b->sim) return aec_fail(ASP_ERR_STATE, "AspAecBatch_ImportState: control-only handle");
   if (!b || !in || stream < 0 || stream >= b->S) return aec_fail(ASP_ERR_PARAM, "ImportState: bad argument");
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   AEC_TRY(hipStreamSynchronize(b->stream));
   const int kStateDwords = state_dwords(b);
   std::vector<float> blk(kStateDwords), cur(kStateDwords);
@@ -1985,7 +1970,7 @@ int AspAecBatch_enable_delay_correction(AspAecBatch* b, int enable) {
       if (rc != 0) return rc;
     }
     if (!b->sim) {
-      AEC_TRY(hipSetDevice(b->device));
+      AEC_TRY(dev_scope_.select(b->device));
       AEC_TRY(hipStreamSynchronize(b->stream));
       const int od = state_dwords(b), nd = AecRows(np).state_dwords;
       std::vector<float> old_all((size_t)b->S * od), new_all((size_t)b->S * nd);
@@ -2010,7 +1995,7 @@ int AspAecBatch_enable_delay_correction(AspAecBatch* b, int enable) {
   b->extended = enable;  // the reference stores the argument as given
   if (!b->sim) {  // WebRtc_set_allowed_offset(delay_estimator, num_partitions / 2), aec_core.c:1880
     std::vector<int32_t> v((size_t)b->S, b->num_part / 2);
-    AEC_TRY(hipSetDevice(b->device));
+    AEC_TRY(dev_scope_.select(b->device));
     AEC_TRY(hipStreamSynchronize(b->stream));
     AEC_TRY(hipMemcpy2D(reinterpret_cast<char*>(b->dblocks) + offsetof(DelayBlock, s.allowed_offset), sizeof(DelayBlock), v.data(),
                         sizeof(int32_t), sizeof(int32_t), (size_t)b->S, hipMemcpyHostToDevice));
@@ -2042,7 +2027,7 @@ int AspAecBatch_ExportDelayState(AspAecBatch* b, int stream, AspAecDelayState* o
   AspDeviceScope dev_scope_;
   if (b && b->sim) return aec_fail(ASP_ERR_STATE, "AspAecBatch_ExportDelayState: control-only handle");
   if (!b || !out || stream < 0 || stream >= b->S) return aec_fail(ASP_ERR_PARAM, "ExportDelayState: bad argument");
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   if (b->agn_synced && b->nevents > 0) {  // far-end calls the streams' read sides have not seen yet
     const int rc = flush_far_events(b);
     if (rc != 0) return rc;
@@ -2077,7 +2062,7 @@ int AspAecBatch_GetDelayMetrics(AspAecBatch* b, int* median, int* std) {
     b->lastError = AEC_UNSUPPORTED_FUNCTION_ERROR;  // logging disabled
     return -1;
   }
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   AEC_TRY(hipStreamSynchronize(b->stream));
   constexpr int H = ASP_AEC_DELAY_HISTORY;
   std::vector<int32_t> hist((size_t)b->S * H), look((size_t)b->S);
@@ -2164,7 +2149,7 @@ int AspAecBatch_get_echo_status(AspAecBatch* b, int* status) {
     b->lastError = AEC_UNINITIALIZED_ERROR;
     return -1;
   }
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   AEC_TRY(hipStreamSynchronize(b->stream));
   for (int s = 0; s < b->S; ++s) {
     int32_t v = 0;
@@ -2190,6 +2175,7 @@ void level_of(const AspAecStats& s, AecLevel* out) {  // echo_cancellation.c:484
 }  // namespace
 
 int AspAecBatch_GetMetrics(AspAecBatch* b, AecMetrics* out) {  // WebRtcAec_GetMetrics, echo_cancellation.c:456-548
+  AspDeviceScope dev_scope_;
   if (b && b->sim) return aec_fail(ASP_ERR_STATE, "AspAecBatch_GetMetrics: control-only handle");
   if (!b) return aec_fail(ASP_ERR_PARAM, "null batch handle");
   if (out == nullptr) {
@@ -2200,7 +2186,7 @@ int AspAecBatch_GetMetrics(AspAecBatch* b, AecMetrics* out) {  // WebRtcAec_GetM
     b->lastError = AEC_UNINITIALIZED_ERROR;
     return -1;
   }
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   AEC_TRY(hipStreamSynchronize(b->stream));
   std::vector<float> all((size_t)b->S * kMetDwords);
   AEC_TRY(hipMemcpy(all.data(), b->metrics, all.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -2224,7 +2210,7 @@ int AspAecBatch_ExportMetricsState(AspAecBatch* b, int stream, AspAecMetricsStat
   AspDeviceScope dev_scope_;
   if (b && b->sim) return aec_fail(ASP_ERR_STATE, "AspAecBatch_ExportMetricsState: control-only handle");
   if (!b || !out || stream < 0 || stream >= b->S) return aec_fail(ASP_ERR_PARAM, "ExportMetricsState: bad argument");
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   AEC_TRY(hipStreamSynchronize(b->stream));
   AEC_TRY(hipMemcpy(out, b->metrics + (size_t)stream * kMetDwords, sizeof *out, hipMemcpyDeviceToHost));
   return 0;
@@ -2236,7 +2222,7 @@ int AspAecBatch_DebugStamps(AspAecBatch* b, const float* far_dev, const float* n
                             unsigned long long* stamps16) {
   AspDeviceScope dev_scope_;
   if (!b || !far_dev || !near_dev || !out_dev || !stamps16) return aec_fail(ASP_ERR_PARAM, "DebugStamps: bad argument");
-  AEC_TRY(hipSetDevice(b->device));
+  AEC_TRY(dev_scope_.select(b->device));
   unsigned long long* d = nullptr;
   AEC_TRY(hipMalloc((void**)&d, 16 * sizeof(unsigned long long)));
   hipError_t e = hipMemset(d, 0, 16 * sizeof(unsigned long long));
@@ -2257,10 +2243,8 @@ int AspAecBatch_DebugStamps(AspAecBatch* b, const float* far_dev, const float* n
 int AspAec_rdft128_batch(const float* src, float* dst, int isgn, int count, int device) {
   AspDeviceScope dev_scope_;
   if (!src || !dst || count <= 0) return aec_fail(ASP_ERR_PARAM, "rdft128_batch: bad argument");
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-    return aec_fail(ASP_ERR_NO_DEVICE, "no HIP device: the echo canceller has no CPU fallback");
-  AEC_TRY(hipSetDevice(device));
+  // an ordinal out of range is reported as the HIP failure it has always been
+  if (int rc = dev_scope_.select("asp_aec", device, ASP_ERR_HIP, "no HIP device: the echo canceller has no CPU fallback")) return rc;
   float *d_in = nullptr, *d_out = nullptr;
   AecTables* d_t = nullptr;
   const size_t bytes = (size_t)count * 128 * sizeof(float);
@@ -2286,10 +2270,8 @@ int AspAec_delay_estimator_batch(AspAecDelayState* states, int count, const uint
   AspDeviceScope dev_scope_;
   if (!states || !binary_far || !binary_near || count <= 0 || nblocks < 0)
     return aec_fail(ASP_ERR_PARAM, "delay_estimator_batch: bad argument");
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-    return aec_fail(ASP_ERR_NO_DEVICE, "no HIP device: the echo canceller has no CPU fallback");
-  AEC_TRY(hipSetDevice(device));
+  // an ordinal out of range is reported as the HIP failure it has always been
+  if (int rc = dev_scope_.select("asp_aec", device, ASP_ERR_HIP, "no HIP device: the echo canceller has no CPU fallback")) return rc;
   std::vector<DelayBlock> blocks((size_t)count);
   for (int i = 0; i < count; ++i) {
     memset(&blocks[i], 0, sizeof(DelayBlock));
@@ -2459,7 +2441,7 @@ void WebRtcAec_SetSystemDelay(struct AecCore* self, int delay) {
   b->system_delay = delay;
   if (b->agn_synced && !b->sim) {
     std::vector<int32_t> v((size_t)b->S, delay);
-    if (hipSetDevice(b->device) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) return;
+    if (dev_scope_.select(b->device) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) return;
     (void)hipMemcpy2D(reinterpret_cast<char*>(b->dblocks) + offsetof(DelayBlock, s.system_delay), sizeof(DelayBlock), v.data(),
                       sizeof(int32_t), sizeof(int32_t), (size_t)b->S, hipMemcpyHostToDevice);
   }

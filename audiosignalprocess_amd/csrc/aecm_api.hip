@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "aecm_layout.h"
+#include "api_common.h"
 
 namespace aspaecm {
 hipError_t launch_frames(AspAecmState* st, AecmWork* wk, const AecmTables* T, int S, int F, int n,
@@ -22,33 +23,8 @@ hipError_t launch_control(AspAecmState* st, const AecmTables* T, int first, int 
 
 using namespace aspaecm;
 
-namespace {
-thread_local char g_aecm_err[512] = "";
-int aecm_fail(int code, const char* what, hipError_t e = hipSuccess) {
-  if (e != hipSuccess)
-    snprintf(g_aecm_err, sizeof g_aecm_err, "%s: %s", what, hipGetErrorString(e));
-  else
-    snprintf(g_aecm_err, sizeof g_aecm_err, "%s", what);
-  fprintf(stderr, "asp_aecm: %s\n", g_aecm_err);
-  return code;
-}
-#define AECM_TRY(expr)                                              \
-  do {                                                              \
-    hipError_t e_ = (expr);                                         \
-    if (e_ != hipSuccess) return aecm_fail(ASP_ERR_HIP, #expr, e_); \
-  } while (0)
-
-hipError_t reserve(void** p, size_t* cap, size_t bytes) {
-  if (*cap >= bytes) return hipSuccess;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipSuccess) *cap = bytes;
-  return e;
-}
-
-}  // namespace
+#define aecm_fail(...) asp_fail("asp_aecm", __VA_ARGS__)
+#define AECM_TRY(x) ASP_TRY("asp_aecm", x)
 
 struct AspAecmBatch {
   int S = 0, device = 0;
@@ -60,21 +36,20 @@ struct AspAecmBatch {
   std::vector<int32_t> last_error;    // lastError, per stream
   std::vector<int16_t> cng, echo;     // the configuration, per stream (get_config)
   std::vector<int16_t> ms_host;       // clamped msInSndCardBuf staging
-  void *s_far = nullptr, *s_near = nullptr, *s_clean = nullptr, *s_out = nullptr, *s_ms = nullptr,
-       *s_path = nullptr;
-  size_t c_far = 0, c_near = 0, c_clean = 0, c_out = 0, c_ms = 0, c_path = 0;
+  AspStage s_far, s_near, s_clean, s_out, s_ms, s_path;  // staging for host-memory callers
 };
 
 namespace {
 int check_stream(AspAecmBatch* b, int s) { return (b && s >= 0 && s < b->S) ? ASP_OK : ASP_ERR_PARAM; }
 
 int control(AspAecmBatch* b, int first, int count, int op, int arg, const int16_t* path_host) {
-  AECM_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  AECM_TRY(dev_scope_.select(b->device));
   const int16_t* path = nullptr;
   if (path_host) {
-    AECM_TRY(reserve(&b->s_path, &b->c_path, 65 * sizeof(int16_t)));
-    AECM_TRY(hipMemcpyAsync(b->s_path, path_host, 65 * sizeof(int16_t), hipMemcpyHostToDevice, b->stream));
-    path = (const int16_t*)b->s_path;
+    AECM_TRY(b->s_path.reserve(65 * sizeof(int16_t)));
+    AECM_TRY(hipMemcpyAsync(b->s_path.p, path_host, 65 * sizeof(int16_t), hipMemcpyHostToDevice, b->stream));
+    path = (const int16_t*)b->s_path.p;
   }
   AECM_TRY(launch_control(b->state, b->tables, first, count, op, arg, path, b->stream));
   if (path_host) AECM_TRY(hipStreamSynchronize(b->stream));  // the staging buffer is reused
@@ -108,33 +83,34 @@ int run_frames(AspAecmBatch* b, int F, const int16_t* far, const int16_t* near, 
       if (ret) ret[i] = r;
     }
   }
-  AECM_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  AECM_TRY(dev_scope_.select(b->device));
   const int16_t *d_far = far, *d_near = near, *d_clean = clean;
   int16_t* d_out = out;
   if (mem == ASP_MEM_HOST) {
     if (far) {
-      AECM_TRY(reserve(&b->s_far, &b->c_far, bytes));
-      AECM_TRY(hipMemcpyAsync(b->s_far, far, bytes, hipMemcpyHostToDevice, b->stream));
-      d_far = (const int16_t*)b->s_far;
+      AECM_TRY(b->s_far.reserve(bytes));
+      AECM_TRY(hipMemcpyAsync(b->s_far.p, far, bytes, hipMemcpyHostToDevice, b->stream));
+      d_far = (const int16_t*)b->s_far.p;
     }
     if (near) {
-      AECM_TRY(reserve(&b->s_near, &b->c_near, bytes));
-      AECM_TRY(hipMemcpyAsync(b->s_near, near, bytes, hipMemcpyHostToDevice, b->stream));
-      d_near = (const int16_t*)b->s_near;
-      AECM_TRY(reserve(&b->s_out, &b->c_out, bytes));
-      d_out = (int16_t*)b->s_out;
+      AECM_TRY(b->s_near.reserve(bytes));
+      AECM_TRY(hipMemcpyAsync(b->s_near.p, near, bytes, hipMemcpyHostToDevice, b->stream));
+      d_near = (const int16_t*)b->s_near.p;
+      AECM_TRY(b->s_out.reserve(bytes));
+      d_out = (int16_t*)b->s_out.p;
     }
     if (clean) {
-      AECM_TRY(reserve(&b->s_clean, &b->c_clean, bytes));
-      AECM_TRY(hipMemcpyAsync(b->s_clean, clean, bytes, hipMemcpyHostToDevice, b->stream));
-      d_clean = (const int16_t*)b->s_clean;
+      AECM_TRY(b->s_clean.reserve(bytes));
+      AECM_TRY(hipMemcpyAsync(b->s_clean.p, clean, bytes, hipMemcpyHostToDevice, b->stream));
+      d_clean = (const int16_t*)b->s_clean.p;
     }
   }
   const int16_t* d_ms = nullptr;
   if (near) {
-    AECM_TRY(reserve(&b->s_ms, &b->c_ms, frames * sizeof(int16_t)));
-    AECM_TRY(hipMemcpyAsync(b->s_ms, b->ms_host.data(), frames * sizeof(int16_t), hipMemcpyHostToDevice, b->stream));
-    d_ms = (const int16_t*)b->s_ms;
+    AECM_TRY(b->s_ms.reserve(frames * sizeof(int16_t)));
+    AECM_TRY(hipMemcpyAsync(b->s_ms.p, b->ms_host.data(), frames * sizeof(int16_t), hipMemcpyHostToDevice, b->stream));
+    d_ms = (const int16_t*)b->s_ms.p;
   }
   AECM_TRY(launch_frames(b->state, b->work, b->tables, S, F, n, d_far, d_near, d_clean, d_out, d_ms, b->stream));
   if (mem == ASP_MEM_HOST && near)
@@ -152,9 +128,8 @@ size_t AspAecm_state_size(void) { return sizeof(AspAecmState); }
 int AspAecmBatch_Create(AspAecmBatch** out, int num_streams, int device) {
   if (!out || num_streams < 1) return ASP_ERR_PARAM;
   *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1 || device < 0 || device >= n)
-    return aecm_fail(ASP_ERR_NO_DEVICE, "AspAecmBatch_Create: no HIP device");
+  AspDeviceScope dev_scope_;
+  if (int rc = dev_scope_.select("asp_aecm", device, ASP_ERR_NO_DEVICE, "AspAecmBatch_Create: no HIP device")) return rc;
   AspAecmBatch* b = new AspAecmBatch;
   b->S = num_streams;
   b->device = device;
@@ -164,8 +139,7 @@ int AspAecmBatch_Create(AspAecmBatch** out, int num_streams, int device) {
   b->echo.assign(num_streams, 3);
   AecmTables T;
   build_tables(&T);
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
+  hipError_t e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipMalloc((void**)&b->state, sizeof(AspAecmState) * (size_t)num_streams);
   if (e == hipSuccess) e = hipMalloc((void**)&b->work, sizeof(AecmWork) * (size_t)num_streams);
   if (e == hipSuccess) e = hipMalloc((void**)&b->tables, sizeof(AecmTables));
@@ -182,9 +156,10 @@ int AspAecmBatch_Create(AspAecmBatch** out, int num_streams, int device) {
 
 int AspAecmBatch_Free(AspAecmBatch* b) {
   if (!b) return ASP_ERR_PARAM;
-  (void)hipSetDevice(b->device);
+  AspDeviceScope dev_scope_;
+  (void)dev_scope_.select(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
-  void* bufs[] = {b->state, b->work, b->tables, b->s_far, b->s_near, b->s_clean, b->s_out, b->s_ms, b->s_path};
+  void* bufs[] = {b->state, b->work, b->tables, b->s_far.p, b->s_near.p, b->s_clean.p, b->s_out.p, b->s_ms.p, b->s_path.p};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -273,7 +248,8 @@ int AspAecmBatch_InitEchoPath_stream(AspAecmBatch* b, int stream, const int16_t*
 int AspAecmBatch_GetEchoPath_stream(AspAecmBatch* b, int stream, int16_t* path) {
   if (check_stream(b, stream) || !path) return ASP_ERR_PARAM;
   if (!b->inited[stream]) return ASP_ERR_STATE;
-  AECM_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  AECM_TRY(dev_scope_.select(b->device));
   AECM_TRY(hipMemcpyAsync(path, &b->state[stream].channelStored[0], 65 * sizeof(int16_t), hipMemcpyDeviceToHost,
                           b->stream));
   AECM_TRY(hipStreamSynchronize(b->stream));
@@ -311,7 +287,8 @@ int AspAecmBatch_get_error_code(AspAecmBatch* b, int stream) {
 
 int AspAecmBatch_ExportState(AspAecmBatch* b, int stream, AspAecmState* out) {
   if (check_stream(b, stream) || !out) return ASP_ERR_PARAM;
-  AECM_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  AECM_TRY(dev_scope_.select(b->device));
   AECM_TRY(hipMemcpyAsync(out, &b->state[stream], sizeof(AspAecmState), hipMemcpyDeviceToHost, b->stream));
   AECM_TRY(hipStreamSynchronize(b->stream));
   return ASP_OK;
@@ -320,7 +297,8 @@ int AspAecmBatch_ExportState(AspAecmBatch* b, int stream, AspAecmState* out) {
 int AspAecmBatch_ImportState(AspAecmBatch* b, int stream, const AspAecmState* in) {
   if (check_stream(b, stream) || !in) return ASP_ERR_PARAM;
   if ((in->sampFreq != 8000 && in->sampFreq != 16000) || in->mult != in->sampFreq / 8000) return ASP_ERR_PARAM;
-  AECM_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  AECM_TRY(dev_scope_.select(b->device));
   AECM_TRY(hipMemcpyAsync(&b->state[stream], in, sizeof(AspAecmState), hipMemcpyHostToDevice, b->stream));
   AECM_TRY(hipStreamSynchronize(b->stream));
   b->inited[stream] = 1;
@@ -337,7 +315,8 @@ int AspAecmBatch_SetStream(AspAecmBatch* b, void* hip_stream) {
 
 int AspAecmBatch_Synchronize(AspAecmBatch* b) {
   if (!b) return ASP_ERR_PARAM;
-  AECM_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  AECM_TRY(dev_scope_.select(b->device));
   AECM_TRY(hipStreamSynchronize(b->stream));
   return ASP_OK;
 }

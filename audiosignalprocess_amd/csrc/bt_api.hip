@@ -3,7 +3,7 @@
 // implemented as a batch of one with host-side hop buffering.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include "device_scope.h"
+#include "api_common.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -39,20 +39,8 @@ hipError_t launch_bt_fftr_any(const BtAnyTables& A, const float* src, float* dst
 
 namespace {
 
-thread_local char g_bt_err[512] = "";
-int bt_fail(int code, const char* what, hipError_t e = hipSuccess) {
-  if (e != hipSuccess)
-    snprintf(g_bt_err, sizeof g_bt_err, "%s: %s", what, hipGetErrorString(e));
-  else
-    snprintf(g_bt_err, sizeof g_bt_err, "%s", what);
-  fprintf(stderr, "asp_bt: %s\n", g_bt_err);
-  return code;
-}
-#define BT_TRY(expr)                                            \
-  do {                                                          \
-    hipError_t e_ = (expr);                                     \
-    if (e_ != hipSuccess) return bt_fail(ASP_ERR_HIP, #expr, e_); \
-  } while (0)
+#define bt_fail(...) asp_fail("asp_bt", __VA_ARGS__)
+#define BT_TRY(x) ASP_TRY("asp_bt", x)
 
 // NOTE: C++ translation unit; every libm call casts to double explicitly so the
 // arithmetic is that of the reference's C (see ns_api.hip).
@@ -229,16 +217,6 @@ int bt_tables(int device, BtTables** out) {
   return ASP_OK;
 }
 
-int bt_select_device(int device) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    return bt_fail(ASP_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)", e);
-  if (device < 0 || device >= n) return bt_fail(ASP_ERR_PARAM, "device ordinal out of range");
-  BT_TRY(hipSetDevice(device));
-  return ASP_OK;
-}
-
 }  // namespace
 
 struct AspBtBatch {
@@ -300,7 +278,7 @@ int AspBtBatch_Create(AspBtBatch** out, int num_streams, int win_size, int devic
   const bool any = win_size != 256 && win_size != 1024;
   if (any && !bt_any_window_ok(win_size))
     return bt_fail(ASP_ERR_PARAM, "AspBtBatch_Create: win_size must be even, 4 .. 2048, with no prime factor of win_size / 2 above 32");
-  int rc = bt_select_device(device);
+  int rc = dev_scope_.select("asp_bt", device, ASP_ERR_PARAM, "no HIP device available (no CPU fallback)");
   if (rc) return rc;
   AspBtBatch* b = new AspBtBatch();
   b->S = num_streams;
@@ -335,7 +313,7 @@ int AspBtBatch_Create(AspBtBatch** out, int num_streams, int win_size, int devic
 int AspBtBatch_Free(AspBtBatch* b) {
   AspDeviceScope dev_scope_;
   if (!b) return ASP_OK;
-  (void)hipSetDevice(b->device);
+  (void)dev_scope_.select(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->state) (void)hipFree(b->state);
   if (b->any_block) (void)hipFree(b->any_block);
@@ -358,7 +336,7 @@ int AspBtBatch_Free(AspBtBatch* b) {
 int AspBtBatch_Reset(AspBtBatch* b) {
   AspDeviceScope dev_scope_;
   if (!b) return bt_fail(ASP_ERR_PARAM, "null batch handle");
-  BT_TRY(hipSetDevice(b->device));
+  BT_TRY(dev_scope_.select(b->device));
   BT_TRY(hipMemsetAsync(b->state, 0, (size_t)b->S * b->state_floats * 4, b->stream));
   return ASP_OK;
 }
@@ -369,7 +347,7 @@ int AspBtBatch_ResetStream(AspBtBatch* b, int stream) {
   AspDeviceScope dev_scope_;
   if (!b) return bt_fail(ASP_ERR_PARAM, "null batch handle");
   if (stream < 0 || stream >= b->S) return bt_fail(ASP_ERR_PARAM, "ResetStream: stream out of range");
-  BT_TRY(hipSetDevice(b->device));
+  BT_TRY(dev_scope_.select(b->device));
   BT_TRY(hipMemsetAsync(b->state + (size_t)stream * b->state_floats, 0, (size_t)b->state_floats * 4, b->stream));
   return ASP_OK;
 }
@@ -387,10 +365,10 @@ static hipError_t bt_launch(AspBtBatch* b, float* state, const float* in, float*
                               s, stamps);
 }
 
-static int bt_run(AspBtBatch* b, const float* in, float* out, int frames, int threshold, int mem) {
+static int bt_run(AspBtBatch* b, AspDeviceScope& dev_scope_, const float* in, float* out, int frames, int threshold, int mem) {
   if (!b || !out || (!in && frames > 0)) return bt_fail(ASP_ERR_PARAM, "null argument");
   if (frames < 0 || frames > 8) return bt_fail(ASP_ERR_PARAM, "frames must be 0..8");
-  BT_TRY(hipSetDevice(b->device));
+  BT_TRY(dev_scope_.select(b->device));
   const int n = frames * b->half;
   const float* din = in;
   float* dout = out;
@@ -419,19 +397,19 @@ static int bt_run(AspBtBatch* b, const float* in, float* out, int frames, int th
 
 int AspBtBatch_Denoise(AspBtBatch* b, const float* in, float* out, int mem) {
   AspDeviceScope dev_scope_;
-  return bt_run(b, in, out, 8, 1, mem);
+  return bt_run(b, dev_scope_, in, out, 8, 1, mem);
 }
 
 int AspBtBatch_Flush(AspBtBatch* b, const float* in, int hops, float* out, int mem) {
   AspDeviceScope dev_scope_;
   if (hops < 0 || hops > 7) return bt_fail(ASP_ERR_PARAM, "Flush: hops must be 0..7");
-  return bt_run(b, in, out, hops, 0, mem);
+  return bt_run(b, dev_scope_, in, out, hops, 0, mem);
 }
 
 int AspBtBatch_Synchronize(AspBtBatch* b) {
   AspDeviceScope dev_scope_;
   if (!b) return bt_fail(ASP_ERR_PARAM, "null batch handle");
-  BT_TRY(hipSetDevice(b->device));
+  BT_TRY(dev_scope_.select(b->device));
   BT_TRY(hipStreamSynchronize(b->stream));
   return bt_flow_check(b);
 }
@@ -450,7 +428,7 @@ int AspBtBatch_DenoiseBlocks(AspBtBatch* b, const float* in, float* out, int nbl
   if (!b || !in || !out || nblocks < 0) return bt_fail(ASP_ERR_PARAM, "DenoiseBlocks: bad argument");
   if (mem != ASP_MEM_HOST && mem != ASP_MEM_DEVICE) return bt_fail(ASP_ERR_PARAM, "mem must be ASP_MEM_HOST or ASP_MEM_DEVICE");
   if (nblocks == 0) return ASP_OK;
-  BT_TRY(hipSetDevice(b->device));
+  BT_TRY(dev_scope_.select(b->device));
   const size_t per = (size_t)b->S * b->macro;
   const float* din = in;
   float* dout = out;
@@ -492,7 +470,7 @@ int AspBtBatch_TimedSteps(AspBtBatch* b, const float* in, float* out, int blocks
   AspDeviceScope dev_scope_;
   if (!b || !in || !out || blocks_in_ring <= 0 || steps < 0 || !elapsed_ms)
     return bt_fail(ASP_ERR_PARAM, "TimedSteps: bad argument");
-  BT_TRY(hipSetDevice(b->device));
+  BT_TRY(dev_scope_.select(b->device));
   const size_t per = (size_t)b->S * b->macro;
   if (bt_flow_applies(b, steps, in, out)) {
     BT_TRY(hipEventRecord(b->ev0, b->stream));
@@ -539,7 +517,8 @@ int AspBtBatch_TimedSteps(AspBtBatch* b, const float* in, float* out, int blocks
 int AspBtBatch_DebugStamps(AspBtBatch* b, const float* in_dev, float* out_dev,
                            unsigned long long* stamps11) {  // 48 slots (0..10 phases, 11..15 sub-phases, 16..47 per-wave stamps of the N = 1024 kernel)
   if (!b || !in_dev || !out_dev || !stamps11) return bt_fail(ASP_ERR_PARAM, "DebugStamps: bad argument");
-  BT_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  BT_TRY(dev_scope_.select(b->device));
   unsigned long long* d = nullptr;
   BT_TRY(hipMalloc((void**)&d, 48 * sizeof(unsigned long long)));
   hipError_t e = hipMemset(d, 0, 48 * sizeof(unsigned long long));
@@ -555,7 +534,7 @@ int AspBtBatch_DebugStamps(AspBtBatch* b, const float* in_dev, float* out_dev,
 int AspBtBatch_ExportState(AspBtBatch* b, int stream, AspBtState* out) {
   AspDeviceScope dev_scope_;
   if (!b || !out || stream < 0 || stream >= b->S) return bt_fail(ASP_ERR_PARAM, "ExportState: bad argument");
-  BT_TRY(hipSetDevice(b->device));
+  BT_TRY(dev_scope_.select(b->device));
   BT_TRY(hipStreamSynchronize(b->stream));
   {
     const int rcf = bt_flow_check(b);
@@ -574,7 +553,7 @@ int AspBtBatch_ImportState(AspBtBatch* b, int stream, const AspBtState* in) {
   AspDeviceScope dev_scope_;
   if (!b || !in || stream < 0 || stream >= b->S) return bt_fail(ASP_ERR_PARAM, "ImportState: bad argument");
   if (in->win_size != b->win) return bt_fail(ASP_ERR_PARAM, "ImportState: win_size mismatch");
-  BT_TRY(hipSetDevice(b->device));
+  BT_TRY(dev_scope_.select(b->device));
   BT_TRY(hipStreamSynchronize(b->stream));
   float blk[kAnyStateFloats];
   memset(blk, 0, sizeof blk);
@@ -588,7 +567,8 @@ static int bt_fft_seam(const float* src, float* dst, int n, int count, int inver
   const bool any = n != 256 && n != 1024;
   if (!src || !dst || count <= 0 || (any && !bt_any_window_ok(n)))
     return bt_fail(ASP_ERR_PARAM, "kiss_fftr seam: bad argument");
-  int rc = bt_select_device(device);
+  AspDeviceScope dev_scope_;
+  int rc = dev_scope_.select("asp_bt", device, ASP_ERR_PARAM, "no HIP device available (no CPU fallback)");
   if (rc) return rc;
   BtTables* T = nullptr;
   BtAnyTables A;
@@ -611,11 +591,9 @@ static int bt_fft_seam(const float* src, float* dst, int n, int count, int inver
 }
 
 int AspBt_kiss_fftr_batch(const float* timedata, float* freqdata, int n, int count, int device) {
-  AspDeviceScope dev_scope_;
   return bt_fft_seam(timedata, freqdata, n, count, 0, device);
 }
 int AspBt_kiss_fftri_batch(const float* freqdata, float* timedata, int n, int count, int device) {
-  AspDeviceScope dev_scope_;
   return bt_fft_seam(freqdata, timedata, n, count, 1, device);
 }
 

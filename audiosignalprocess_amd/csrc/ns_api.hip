@@ -16,6 +16,7 @@
 #include <mutex>
 #include <vector>
 
+#include "api_common.h"
 #include "asp_ns.h"
 #include "handoff_host.h"
 #include "ns_layout.h"
@@ -56,21 +57,10 @@ hipError_t launch_debug_compare(int fn_a, int fn_b, unsigned start, unsigned cou
 
 namespace {
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* what, hipError_t e = hipSuccess) {
-  if (e != hipSuccess)
-    snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
-  else
-    snprintf(g_err, sizeof g_err, "%s", what);
-  return code;
-}
-
-#define HIP_TRY(expr)                                         \
-  do {                                                        \
-    hipError_t e_ = (expr);                                   \
-    if (e_ != hipSuccess) return fail(ASP_ERR_HIP, #expr, e_); \
-  } while (0)
+// the NS engine records its failures without printing them
+#define fail(...) asp_fail(nullptr, __VA_ARGS__)
+#define HIP_TRY(x) ASP_TRY(nullptr, x)
+constexpr const char* kNoDevice = "no HIP device available (the NS engine has no CPU fallback)";
 
 // ------------------------------------------------------------------ tables
 
@@ -385,28 +375,6 @@ int device_tables(int device, NsTables** out) {
   return ASP_OK;
 }
 
-// The caller's current device is put back when an entry point returns (every entry point
-// selects the batch's device for its HIP calls).
-struct DeviceScope {
-  int prev = -1;
-  DeviceScope() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceScope() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-int select_device(int device) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    return fail(ASP_ERR_NO_DEVICE, "no HIP device available (the NS engine has no CPU fallback)", e);
-  if (device < 0 || device >= n) return fail(ASP_ERR_PARAM, "device ordinal out of range");
-  e = hipSetDevice(device);
-  if (e != hipSuccess) return fail(ASP_ERR_HIP, "hipSetDevice", e);
-  return ASP_OK;
-}
-
 // --------------------------------------------------- canonical <-> device image
 
 inline float i2f(int32_t v) {
@@ -590,9 +558,7 @@ struct AspNsBatch {
   float* state = nullptr;
   int32_t* hist = nullptr;
   NsTables* tables = nullptr;
-  float* stage_in = nullptr;   // device staging for ASP_MEM_HOST callers
-  float* stage_out = nullptr;
-  size_t stage_frames = 0;
+  AspStage stage_in, stage_out;  // device staging for ASP_MEM_HOST callers
   bool inited = false;
   bool paired = true;  // see ns_kernels.hip: fused step representation
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -637,15 +603,9 @@ struct AspNsBatch {
 namespace {
 
 int ensure_stage(AspNsBatch* b, size_t frames) {
-  if (b->stage_frames >= frames) return ASP_OK;
-  if (b->stage_in) (void)hipFree(b->stage_in);
-  if (b->stage_out) (void)hipFree(b->stage_out);
-  b->stage_in = b->stage_out = nullptr;
-  b->stage_frames = 0;
   const size_t bytes = frames * (size_t)b->S * b->block * sizeof(float);
-  HIP_TRY(hipMalloc((void**)&b->stage_in, bytes));
-  HIP_TRY(hipMalloc((void**)&b->stage_out, bytes));
-  b->stage_frames = frames;
+  HIP_TRY(b->stage_in.reserve(bytes));
+  HIP_TRY(b->stage_out.reserve(bytes));
   return ASP_OK;
 }
 
@@ -656,11 +616,10 @@ int ensure_unpaired(AspNsBatch* b) {
   return ASP_OK;
 }
 
-int check(AspNsBatch* b) {
+int check(AspNsBatch* b, AspDeviceScope& dev_scope_) {
   if (!b) return fail(ASP_ERR_PARAM, "null batch handle");
   if (!b->inited) return fail(ASP_ERR_STATE, "batch not initialised (call AspNsBatch_Init)");
-  hipError_t e = hipSetDevice(b->device);
-  if (e != hipSuccess) return fail(ASP_ERR_HIP, "hipSetDevice", e);
+  HIP_TRY(dev_scope_.select(b->device));
   return ASP_OK;
 }
 
@@ -668,7 +627,7 @@ int check(AspNsBatch* b) {
 
 extern "C" {
 
-const char* AspNs_last_error(void) { return g_err; }
+const char* AspNs_last_error(void) { return asp_last_error(); }
 
 // Host-side copy of the constant tables (window, per-lane twiddles, ...): no
 // device needed, so the CPU test-suite can pin them against the oracle.
@@ -689,8 +648,8 @@ int AspNs_device_count(void) {
 int AspNsBatch_Create(AspNsBatch** out, int num_streams, int device) {
   if (!out || num_streams <= 0) return fail(ASP_ERR_PARAM, "AspNsBatch_Create: bad argument");
   *out = nullptr;
-  DeviceScope dev_scope_;
-  int rc = select_device(device);
+  AspDeviceScope dev_scope_;
+  int rc = dev_scope_.select(nullptr, device, ASP_ERR_PARAM, kNoDevice);
   if (rc) return rc;
   AspNsBatch* b = new AspNsBatch();
   b->S = num_streams;
@@ -716,14 +675,14 @@ int AspNsBatch_Create(AspNsBatch** out, int num_streams, int device) {
 
 int AspNsBatch_Free(AspNsBatch* b) {
   if (!b) return ASP_OK;
-  DeviceScope dev_scope_;
-  (void)hipSetDevice(b->device);
+  AspDeviceScope dev_scope_;
+  (void)dev_scope_.select(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->state) (void)hipFree(b->state);
   if (b->hist) (void)hipFree(b->hist);
   b->sync.release();
-  if (b->stage_in) (void)hipFree(b->stage_in);
-  if (b->stage_out) (void)hipFree(b->stage_out);
+  b->stage_in.release();
+  b->stage_out.release();
   if (b->hb_tail) (void)hipFree(b->hb_tail);
   if (b->hb_live) (void)hipFree(b->hb_live);
   if (b->hb_stage) (void)hipFree(b->hb_stage);
@@ -751,14 +710,8 @@ int AspNsBatch_Init(AspNsBatch* b, uint32_t fs) {
   // and 16 / 32 / 48 kHz (160 / 256 / 129)
   if (fs != 8000 && fs != 16000 && fs != 32000 && fs != 48000)
     return fail(ASP_ERR_PARAM, "AspNsBatch_Init: fs must be 8000, 16000, 32000 or 48000");
-  HIP_TRY(hipSetDevice(b->device));
-  if (b->fs != fs && b->stage_frames) {  // the staging buffers are sized in frames of the old length
-    if (b->stream) HIP_TRY(hipStreamSynchronize(b->stream));
-    if (b->stage_in) (void)hipFree(b->stage_in);
-    if (b->stage_out) (void)hipFree(b->stage_out);
-    b->stage_in = b->stage_out = nullptr;
-    b->stage_frames = 0;
-  }
+  AspDeviceScope dev_scope_;
+  HIP_TRY(dev_scope_.select(b->device));
   b->fs = fs;
   b->block = geo_block((int)fs);
   b->num_high = fs >= 32000 ? (int)(fs / 16000) - 1 : 0;
@@ -798,8 +751,8 @@ static int flow_check(AspNsBatch* b);
 // histograms go back to InitCore's values at the batch's sample rate (policy 0, as InitCore ends,
 // ns_core.c:207); the other streams are untouched.  Ordered on the batch's stream like every other call.
 int AspNsBatch_InitStream(AspNsBatch* b, int stream) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (stream < 0 || stream >= b->S) return fail(ASP_ERR_PARAM, "InitStream: stream out of range");
   std::vector<AspNsState> s0(1);
@@ -823,8 +776,8 @@ static const int kPolicyMap[4] = {0, 1, 1, 1};
 
 // WebRtcNs_set_policy of ONE stream (noise_suppression.c:41-44 per handle).
 int AspNsBatch_set_policy_stream(AspNsBatch* b, int stream, int mode) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (stream < 0 || stream >= b->S) return fail(ASP_ERR_PARAM, "set_policy_stream: stream out of range");
   if (mode < 0 || mode > 3) return fail(ASP_ERR_PARAM, "set_policy: mode must be 0..3");
@@ -834,8 +787,8 @@ int AspNsBatch_set_policy_stream(AspNsBatch* b, int stream, int mode) {
 }
 
 int AspNsBatch_set_policy(AspNsBatch* b, int mode) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (mode < 0 || mode > 3) return fail(ASP_ERR_PARAM, "set_policy: mode must be 0..3");
   // ns_core.c:1020-1039
@@ -1025,10 +978,10 @@ static int run_frames(AspNsBatch* b, int kmode, const float* in, float* out, int
   if (mem == ASP_MEM_HOST) {
     int rc = ensure_stage(b, (size_t)num_frames);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(b->stage_in, in, per * num_frames * 4, hipMemcpyHostToDevice,
+    HIP_TRY(hipMemcpyAsync(b->stage_in.p, in, per * num_frames * 4, hipMemcpyHostToDevice,
                            b->stream));
-    din = b->stage_in;
-    dout = b->stage_out;
+    din = (float*)b->stage_in.p;
+    dout = (float*)b->stage_out.p;
   } else if (mem != ASP_MEM_DEVICE) {
     return fail(ASP_ERR_PARAM, "mem must be ASP_MEM_HOST or ASP_MEM_DEVICE");
   }
@@ -1048,7 +1001,7 @@ static int run_frames(AspNsBatch* b, int kmode, const float* in, float* out, int
   }
   if (mem == ASP_MEM_HOST) {
     if (out && kmode != 0)
-      HIP_TRY(hipMemcpyAsync(out, b->stage_out, per * num_frames * 4, hipMemcpyDeviceToHost,
+      HIP_TRY(hipMemcpyAsync(out, b->stage_out.p, per * num_frames * 4, hipMemcpyDeviceToHost,
                              b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return flow_check(b);
@@ -1057,8 +1010,8 @@ static int run_frames(AspNsBatch* b, int kmode, const float* in, float* out, int
 }
 
 int AspNsBatch_Analyze(AspNsBatch* b, const float* frames, int mem) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!frames) return fail(ASP_ERR_PARAM, "Analyze: null frames");
   rc = ensure_unpaired(b);
@@ -1067,8 +1020,8 @@ int AspNsBatch_Analyze(AspNsBatch* b, const float* frames, int mem) {
 }
 
 int AspNsBatch_Process(AspNsBatch* b, const float* in, float* out, int mem) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!in || !out) return fail(ASP_ERR_PARAM, "Process: null frames");
   rc = ensure_unpaired(b);
@@ -1078,8 +1031,8 @@ int AspNsBatch_Process(AspNsBatch* b, const float* in, float* out, int mem) {
 
 int AspNsBatch_AnalyzeProcess(AspNsBatch* b, const float* in, float* out, int num_frames,
                               int mem) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!in || !out || num_frames < 0) return fail(ASP_ERR_PARAM, "AnalyzeProcess: bad argument");
   if (b->num_high > 0)  // the high-band delay line would fall out of step (ns_core.c:1227-1235)
@@ -1107,8 +1060,8 @@ static int bands_frame_device(AspNsBatch* b, bool fused, const float* low_in, co
 
 static int bands_run(AspNsBatch* b, bool fused, const float* low_in, const float* high_in,
                      float* low_out, float* high_out, int num_frames, int mem) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (b->num_high < 1) return fail(ASP_ERR_STATE, "bands: the batch was initialised at 16 kHz (one band)");
   if (!low_in || !high_in || !low_out || !high_out || num_frames < 0)
@@ -1128,11 +1081,11 @@ static int bands_run(AspNsBatch* b, bool fused, const float* low_in, const float
   float* hin = b->hb_stage;
   float* hout = b->hb_stage + (size_t)2 * lper;
   for (int f = 0; f < num_frames; ++f) {
-    HIP_TRY(hipMemcpyAsync(b->stage_in, low_in + lper * f, lper * 4, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->stage_in.p, low_in + lper * f, lper * 4, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipMemcpyAsync(hin, high_in + hper * f, hper * 4, hipMemcpyHostToDevice, b->stream));
-    rc = bands_frame_device(b, fused, b->stage_in, hin, b->stage_out, hout);
+    rc = bands_frame_device(b, fused, (float*)b->stage_in.p, hin, (float*)b->stage_out.p, hout);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(low_out + lper * f, b->stage_out, lper * 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(low_out + lper * f, b->stage_out.p, lper * 4, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipMemcpyAsync(high_out + hper * f, hout, hper * 4, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
   }
@@ -1141,16 +1094,16 @@ static int bands_run(AspNsBatch* b, bool fused, const float* low_in, const float
 
 int AspNsBatch_AnalyzeProcessBands(AspNsBatch* b, const float* low_in, const float* high_in,
                                    float* low_out, float* high_out, int num_frames, int mem) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   return bands_run(b, true, low_in, high_in, low_out, high_out, num_frames, mem);
 }
 
 int AspNsBatch_ProcessBands(AspNsBatch* b, const float* low_in, const float* high_in, float* low_out,
                             float* high_out, int mem) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   rc = ensure_unpaired(b);
   if (rc) return rc;
@@ -1160,8 +1113,8 @@ int AspNsBatch_ProcessBands(AspNsBatch* b, const float* low_in, const float* hig
 int AspNsBatch_num_bands(const AspNsBatch* b) { return b ? 1 + b->num_high : ASP_ERR_PARAM; }
 
 int AspNsBatch_ExportHbState(AspNsBatch* b, int stream, AspNsHbState* out) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!out || stream < 0 || stream >= b->S || b->num_high < 1)
     return fail(ASP_ERR_PARAM, "ExportHbState: bad argument");
@@ -1174,8 +1127,8 @@ int AspNsBatch_ExportHbState(AspNsBatch* b, int stream, AspNsHbState* out) {
 }
 
 int AspNsBatch_ImportHbState(AspNsBatch* b, int stream, const AspNsHbState* in) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!in || stream < 0 || stream >= b->S || b->num_high < 1)
     return fail(ASP_ERR_PARAM, "ImportHbState: bad argument");
@@ -1188,8 +1141,8 @@ int AspNsBatch_ImportHbState(AspNsBatch* b, int stream, const AspNsHbState* in) 
 
 int AspNsBatch_AnalyzeProcessS16(AspNsBatch* b, const int16_t* in, int16_t* out, int num_frames,
                                  int mem) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!in || !out || num_frames < 0) return fail(ASP_ERR_PARAM, "AnalyzeProcessS16: bad argument");
   if (!b->paired)
@@ -1203,16 +1156,16 @@ int AspNsBatch_AnalyzeProcessS16(AspNsBatch* b, const int16_t* in, int16_t* out,
   if (mem == ASP_MEM_HOST) {
     rc = ensure_stage(b, (size_t)(num_frames + 1) / 2);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(b->stage_in, in, bytes, hipMemcpyHostToDevice, b->stream));
-    din = b->stage_in;
-    dout = b->stage_out;
+    HIP_TRY(hipMemcpyAsync(b->stage_in.p, in, bytes, hipMemcpyHostToDevice, b->stream));
+    din = (float*)b->stage_in.p;
+    dout = (float*)b->stage_out.p;
   } else if (mem != ASP_MEM_DEVICE) {
     return fail(ASP_ERR_PARAM, "mem must be ASP_MEM_HOST or ASP_MEM_DEVICE");
   }
   rc = fused_steps(b, din, dout, num_frames, num_frames, true);
   if (rc) return rc;
   if (mem == ASP_MEM_HOST) {
-    HIP_TRY(hipMemcpyAsync(out, b->stage_out, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(out, b->stage_out.p, bytes, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return flow_check(b);
   }
@@ -1221,8 +1174,8 @@ int AspNsBatch_AnalyzeProcessS16(AspNsBatch* b, const int16_t* in, int16_t* out,
 
 int AspNsBatch_AnalyzeProcessReplay(AspNsBatch* b, const float* in, float* out, int frames_in_ring,
                                     int steps) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!in || !out || frames_in_ring <= 0 || steps < 0)
     return fail(ASP_ERR_PARAM, "AnalyzeProcessReplay: bad argument");
@@ -1237,8 +1190,8 @@ int AspNsBatch_AnalyzeProcessReplay(AspNsBatch* b, const float* in, float* out, 
 
 int AspNsBatch_TimedSteps(AspNsBatch* b, const float* in, float* out, int frames_in_ring,
                           int steps, float* elapsed_ms) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!in || !out || frames_in_ring <= 0 || steps < 0 || !elapsed_ms)
     return fail(ASP_ERR_PARAM, "TimedSteps: bad argument");
@@ -1267,8 +1220,8 @@ int AspNsBatch_TimedSteps(AspNsBatch* b, const float* in, float* out, int frames
 }
 
 int AspNsBatch_ExportState(AspNsBatch* b, int stream, AspNsState* out) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!out || stream < 0 || stream >= b->S) return fail(ASP_ERR_PARAM, "ExportState: bad argument");
   std::vector<float> blk(kStreamDwords);
@@ -1285,8 +1238,8 @@ int AspNsBatch_ExportState(AspNsBatch* b, int stream, AspNsState* out) {
 }
 
 int AspNsBatch_ImportState(AspNsBatch* b, int stream, const AspNsState* in) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!in || stream < 0 || stream >= b->S) return fail(ASP_ERR_PARAM, "ImportState: bad argument");
   if ((uint32_t)in->fs != b->fs)
@@ -1310,8 +1263,8 @@ int AspNsBatch_ImportState(AspNsBatch* b, int stream, const AspNsState* in) {
 }
 
 int AspNsBatch_prior_speech_probability(AspNsBatch* b, float* out) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!out) return fail(ASP_ERR_PARAM, "null output");
   HIP_TRY(hipStreamSynchronize(b->stream));
@@ -1323,7 +1276,8 @@ int AspNsBatch_prior_speech_probability(AspNsBatch* b, float* out) {
 
 int AspNsBatch_SetSplit(AspNsBatch* b, int parts) {
   if (!b || parts < 1 || parts > 4) return fail(ASP_ERR_PARAM, "SetSplit: parts must be 1..4");
-  HIP_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  HIP_TRY(dev_scope_.select(b->device));
   if (!b->fork_ev) HIP_TRY(hipEventCreateWithFlags(&b->fork_ev, hipEventDisableTiming));
   for (int i = 0; i < parts - 1; ++i) {
     if (!b->side[i]) HIP_TRY(hipStreamCreateWithFlags(&b->side[i], hipStreamNonBlocking));
@@ -1336,8 +1290,8 @@ int AspNsBatch_SetSplit(AspNsBatch* b, int parts) {
 // Diagnostic: one fused step of the pair-layout kernel with the phase stamps of workgroup 0's first wave (16 values).
 int AspNsBatch_DebugStamps(AspNsBatch* b, const float* in_dev, float* out_dev,
                            unsigned long long* stamps16) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!in_dev || !out_dev || !stamps16 || !b->paired || b->kernel == 1 || b->fs == 8000)
     return fail(ASP_ERR_PARAM, "DebugStamps: bad argument (paired state, pair-layout kernel)");
@@ -1358,8 +1312,8 @@ int AspNsBatch_DebugStamps(AspNsBatch* b, const float* in_dev, float* out_dev,
 // phase): kernel start, the 15 phase marks of the frame step, stores drained.
 int AspNsBatch_DebugFlowStamps(AspNsBatch* b, const float* in_dev, float* out_dev, int frames_in_ring, int steps,
                                unsigned long long* stamps17) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!in_dev || !out_dev || !stamps17 || steps < 2 || steps > kHandoffMaxSteps || !flow_applies(b, steps))
     return fail(ASP_ERR_PARAM, "DebugFlowStamps: bad argument (hand-off build, 2..64 steps)");
@@ -1382,8 +1336,8 @@ int AspNsBatch_DebugFlowStamps(AspNsBatch* b, const float* in_dev, float* out_de
 // loads in, before the last stores, end); out[num_workgroups][4] holds those of the last step.
 int AspNsBatch_DebugTimeline(AspNsBatch* b, const float* in_dev, float* out_dev, int frames_in_ring,
                              int steps, unsigned long long* out, int num_workgroups) {
-  DeviceScope dev_scope_;
-  int rc = check(b);
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
   if (rc) return rc;
   if (!in_dev || !out_dev || !out || steps <= 0 || frames_in_ring <= 0 || !b->paired || b->kernel == 1 ||
       b->fs == 8000 || num_workgroups != (b->S + 3) / 4 || (b->S & 3))
@@ -1442,7 +1396,8 @@ int AspNsBatch_SetKernel(AspNsBatch* b, int kernel) {
 
 int AspNsBatch_SetStream(AspNsBatch* b, void* hip_stream) {
   if (!b) return fail(ASP_ERR_PARAM, "null batch handle");
-  (void)hipSetDevice(b->device);
+  AspDeviceScope dev_scope_;
+  (void)dev_scope_.select(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);
   b->stream = (hipStream_t)hip_stream;
@@ -1454,7 +1409,8 @@ void* AspNsBatch_GetStream(AspNsBatch* b) { return b ? (void*)b->stream : nullpt
 
 int AspNsBatch_Synchronize(AspNsBatch* b) {
   if (!b) return fail(ASP_ERR_PARAM, "null batch handle");
-  HIP_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  HIP_TRY(dev_scope_.select(b->device));
   HIP_TRY(hipStreamSynchronize(b->stream));
   return flow_check(b);
 }
@@ -1481,7 +1437,8 @@ __global__ __launch_bounds__(256) void asp_copy_kernel(const float4* __restrict_
 // bytes) / hipEvent time of the best of three timed passes.
 int AspNs_CopyCeiling(size_t bytes, int iters, int device, double* gbps) {
   if (!gbps || bytes < 4096 || (bytes & 15) || iters < 1) return fail(ASP_ERR_PARAM, "CopyCeiling: bad argument");
-  int rc = select_device(device);
+  AspDeviceScope dev_scope_;
+  int rc = dev_scope_.select(nullptr, device, ASP_ERR_PARAM, kNoDevice);
   if (rc) return rc;
   float4 *src = nullptr, *dst = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1516,7 +1473,8 @@ int AspNs_CopyCeiling(size_t bytes, int iters, int device, double* gbps) {
 
 int AspNs_DeviceAlloc(void** ptr, size_t bytes, int device) {
   if (!ptr) return fail(ASP_ERR_PARAM, "null pointer");
-  int rc = select_device(device);
+  AspDeviceScope dev_scope_;
+  int rc = dev_scope_.select(nullptr, device, ASP_ERR_PARAM, kNoDevice);
   if (rc) return rc;
   HIP_TRY(hipMalloc(ptr, bytes));
   return ASP_OK;
@@ -1536,7 +1494,8 @@ int AspNs_MemcpyD2H(void* dst, const void* src, size_t bytes) {
 
 static int rdft_batch(float* data, int count, int isgn, int mem, int device, int n) {
   if (!data || count <= 0) return fail(ASP_ERR_PARAM, "rdft batch: bad argument");
-  int rc = select_device(device);
+  AspDeviceScope dev_scope_;
+  int rc = dev_scope_.select(nullptr, device, ASP_ERR_PARAM, kNoDevice);
   if (rc) return rc;
   NsTables* T = nullptr;
   rc = device_tables(device, &T);
@@ -1570,7 +1529,8 @@ int AspNs_rdft128_batch(float* data, int count, int isgn, int mem, int device) {
 // Test seams for the device math (see debug_fn in ns_kernels.hip).
 int AspNs_debug_eval(int fn, float* data, size_t n, int device) {
   if (!data || n == 0) return fail(ASP_ERR_PARAM, "debug_eval: bad argument");
-  int rc = select_device(device);
+  AspDeviceScope dev_scope_;
+  int rc = dev_scope_.select(nullptr, device, ASP_ERR_PARAM, kNoDevice);
   if (rc) return rc;
   NsTables* T = nullptr;
   rc = device_tables(device, &T);
@@ -1588,7 +1548,8 @@ int AspNs_debug_eval(int fn, float* data, size_t n, int device) {
 int AspNs_debug_compare(int fn_a, int fn_b, uint32_t start, uint32_t count, uint32_t* n_bad,
                         uint32_t* bad_bits64, float param, int device) {
   if (!n_bad || !bad_bits64) return fail(ASP_ERR_PARAM, "debug_compare: bad argument");
-  int rc = select_device(device);
+  AspDeviceScope dev_scope_;
+  int rc = dev_scope_.select(nullptr, device, ASP_ERR_PARAM, kNoDevice);
   if (rc) return rc;
   NsTables* T = nullptr;
   rc = device_tables(device, &T);
@@ -1622,7 +1583,7 @@ int WebRtcNs_Create(NsHandle** NS_inst) {
   h->batch = nullptr;
   h->initFlag = 0;
   if (AspNsBatch_Create(&h->batch, 1, 0) != ASP_OK) {
-    fprintf(stderr, "WebRtcNs_Create: %s\n", g_err);
+    fprintf(stderr, "WebRtcNs_Create: %s\n", asp_last_error());
     free(h);
     *NS_inst = NULL;
     return -1;
@@ -1657,7 +1618,7 @@ void WebRtcNs_Analyze(NsHandle* NS_inst, const float* spframe) {
     abort();
   }
   if (AspNsBatch_Analyze(NS_inst->batch, spframe, ASP_MEM_HOST) != ASP_OK) {
-    fprintf(stderr, "WebRtcNs_Analyze: %s\n", g_err);
+    fprintf(stderr, "WebRtcNs_Analyze: %s\n", asp_last_error());
     abort();
   }
 }
@@ -1677,14 +1638,14 @@ void WebRtcNs_Process(NsHandle* NS_inst, const float* const* spframe, int num_ba
     float hin[2 * kBlockL], hout[2 * kBlockL];
     for (int k = 1; k < num_bands; ++k) memcpy(hin + (k - 1) * kBlockL, spframe[k], kBlockL * sizeof(float));
     if (AspNsBatch_ProcessBands(NS_inst->batch, spframe[0], hin, outframe[0], hout, ASP_MEM_HOST) != ASP_OK) {
-      fprintf(stderr, "WebRtcNs_Process: %s\n", g_err);
+      fprintf(stderr, "WebRtcNs_Process: %s\n", asp_last_error());
       abort();
     }
     for (int k = 1; k < num_bands; ++k) memcpy(outframe[k], hout + (k - 1) * kBlockL, kBlockL * sizeof(float));
     return;
   }
   if (AspNsBatch_Process(NS_inst->batch, spframe[0], outframe[0], ASP_MEM_HOST) != ASP_OK) {
-    fprintf(stderr, "WebRtcNs_Process: %s\n", g_err);
+    fprintf(stderr, "WebRtcNs_Process: %s\n", asp_last_error());
     abort();
   }
 }

@@ -9,6 +9,7 @@
 
 #include <vector>
 
+#include "api_common.h"
 #include "nsx_layout.h"
 
 namespace aspnsx {
@@ -19,32 +20,11 @@ hipError_t launch_control(AspNsxState* st, int first, int count, int op, int arg
 
 using namespace aspnsx;
 
-namespace {
-thread_local char g_nsx_err[512] = "";
-thread_local int g_nsx_refused = 0;
-int nsx_fail(int code, const char* what, hipError_t e = hipSuccess) {
-  if (e != hipSuccess)
-    snprintf(g_nsx_err, sizeof g_nsx_err, "%s: %s", what, hipGetErrorString(e));
-  else
-    snprintf(g_nsx_err, sizeof g_nsx_err, "%s", what);
-  fprintf(stderr, "asp_nsx: %s\n", g_nsx_err);
-  return code;
-}
-#define NSX_TRY(expr)                                             \
-  do {                                                            \
-    hipError_t e_ = (expr);                                       \
-    if (e_ != hipSuccess) return nsx_fail(ASP_ERR_HIP, #expr, e_); \
-  } while (0)
+#define nsx_fail(...) asp_fail("asp_nsx", __VA_ARGS__)
+#define NSX_TRY(x) ASP_TRY("asp_nsx", x)
 
-hipError_t reserve(void** p, size_t* cap, size_t bytes) {
-  if (*cap >= bytes) return hipSuccess;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipSuccess) *cap = bytes;
-  return e;
-}
+namespace {
+thread_local int g_nsx_refused = 0;
 bool valid_fs(uint32_t fs) { return fs == 8000 || fs == 16000 || fs == 32000 || fs == 48000; }
 }  // namespace
 
@@ -54,15 +34,15 @@ struct AspNsxBatch {
   AspNsxState* state = nullptr;  // [S]
   NsxTables* tables = nullptr;
   std::vector<uint32_t> fs;  // per stream; 0: not initialised
-  void *s_li = nullptr, *s_hi = nullptr, *s_lo = nullptr, *s_ho = nullptr;
-  size_t c_li = 0, c_hi = 0, c_lo = 0, c_ho = 0;
+  AspStage s_li, s_hi, s_lo, s_ho;  // staging for host-memory callers
 };
 
 namespace {
 int check_stream(AspNsxBatch* b, int s) { return (b && s >= 0 && s < b->S) ? ASP_OK : ASP_ERR_PARAM; }
 
 int control(AspNsxBatch* b, int first, int count, int op, int arg) {
-  NSX_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  NSX_TRY(dev_scope_.select(b->device));
   NSX_TRY(launch_control(b->state, first, count, op, arg, b->stream));
   return ASP_OK;
 }
@@ -80,21 +60,22 @@ int run_frames(AspNsxBatch* b, int F, const int16_t* li, const int16_t* hi, int1
   if (F == 0) return ASP_OK;
   const int S = b->S;
   const size_t lb = (size_t)F * S * n * sizeof(int16_t), hb = lb * (nb - 1);
-  NSX_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  NSX_TRY(dev_scope_.select(b->device));
   const int16_t *d_li = li, *d_hi = hi;
   int16_t *d_lo = lo, *d_ho = ho;
   if (mem == ASP_MEM_HOST) {
-    NSX_TRY(reserve(&b->s_li, &b->c_li, lb));
-    NSX_TRY(reserve(&b->s_lo, &b->c_lo, lb));
-    NSX_TRY(hipMemcpyAsync(b->s_li, li, lb, hipMemcpyHostToDevice, b->stream));
-    d_li = (const int16_t*)b->s_li;
-    d_lo = (int16_t*)b->s_lo;
+    NSX_TRY(b->s_li.reserve(lb));
+    NSX_TRY(b->s_lo.reserve(lb));
+    NSX_TRY(hipMemcpyAsync(b->s_li.p, li, lb, hipMemcpyHostToDevice, b->stream));
+    d_li = (const int16_t*)b->s_li.p;
+    d_lo = (int16_t*)b->s_lo.p;
     if (nb > 1) {
-      NSX_TRY(reserve(&b->s_hi, &b->c_hi, hb));
-      NSX_TRY(reserve(&b->s_ho, &b->c_ho, hb));
-      NSX_TRY(hipMemcpyAsync(b->s_hi, hi, hb, hipMemcpyHostToDevice, b->stream));
-      d_hi = (const int16_t*)b->s_hi;
-      d_ho = (int16_t*)b->s_ho;
+      NSX_TRY(b->s_hi.reserve(hb));
+      NSX_TRY(b->s_ho.reserve(hb));
+      NSX_TRY(hipMemcpyAsync(b->s_hi.p, hi, hb, hipMemcpyHostToDevice, b->stream));
+      d_hi = (const int16_t*)b->s_hi.p;
+      d_ho = (int16_t*)b->s_ho.p;
     }
   }
   NSX_TRY(launch_frames(b->state, b->tables, S, F, n, nb, d_li, d_hi, d_lo, d_ho, b->stream));
@@ -114,9 +95,10 @@ int AspNsx_last_refused(void) { return g_nsx_refused; }
 
 int AspNsxBatch_Free(AspNsxBatch* b) {
   if (!b) return ASP_ERR_PARAM;
-  (void)hipSetDevice(b->device);
+  AspDeviceScope dev_scope_;
+  (void)dev_scope_.select(b->device);
   if (b->own_stream) (void)hipStreamSynchronize(b->own_stream);
-  void* bufs[] = {b->state, b->tables, b->s_li, b->s_hi, b->s_lo, b->s_ho};
+  void* bufs[] = {b->state, b->tables, b->s_li.p, b->s_hi.p, b->s_lo.p, b->s_ho.p};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -127,17 +109,15 @@ int AspNsxBatch_Free(AspNsxBatch* b) {
 int AspNsxBatch_Create(AspNsxBatch** out, int num_streams, int device) {
   if (!out || num_streams < 1) return ASP_ERR_PARAM;
   *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1 || device < 0 || device >= n)
-    return nsx_fail(ASP_ERR_NO_DEVICE, "AspNsxBatch_Create: no HIP device");
+  AspDeviceScope dev_scope_;
+  if (int rc = dev_scope_.select("asp_nsx", device, ASP_ERR_NO_DEVICE, "AspNsxBatch_Create: no HIP device")) return rc;
   AspNsxBatch* b = new AspNsxBatch;
   b->S = num_streams;
   b->device = device;
   b->fs.assign(num_streams, 0);
   static NsxTables T;
   build_tables(&T);
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
+  hipError_t e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipMalloc((void**)&b->state, sizeof(AspNsxState) * (size_t)num_streams);
   if (e == hipSuccess) e = hipMalloc((void**)&b->tables, sizeof(NsxTables));
   if (e == hipSuccess) e = hipMemset(b->state, 0, sizeof(AspNsxState) * (size_t)num_streams);
@@ -185,7 +165,8 @@ int AspNsxBatch_ProcessFrames(AspNsxBatch* b, int F, const int16_t* li, const in
 
 int AspNsxBatch_ExportState(AspNsxBatch* b, int stream, AspNsxState* out) {
   if (check_stream(b, stream) || !out) return ASP_ERR_PARAM;
-  NSX_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  NSX_TRY(dev_scope_.select(b->device));
   NSX_TRY(hipMemcpyAsync(out, &b->state[stream], sizeof(AspNsxState), hipMemcpyDeviceToHost, b->stream));
   NSX_TRY(hipStreamSynchronize(b->stream));
   return ASP_OK;
@@ -200,7 +181,8 @@ int AspNsxBatch_ImportState(AspNsxBatch* b, int stream, const AspNsxState* in) {
       in->noiseEstCounter[1] < 0 || in->noiseEstCounter[1] > 200 || in->noiseEstCounter[2] < 0 ||
       in->noiseEstCounter[2] > 200 || in->normData < 0 || in->normData > 15)
     return ASP_ERR_PARAM;
-  NSX_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  NSX_TRY(dev_scope_.select(b->device));
   NSX_TRY(hipMemcpyAsync(&b->state[stream], in, sizeof(AspNsxState), hipMemcpyHostToDevice, b->stream));
   NSX_TRY(hipStreamSynchronize(b->stream));
   b->fs[stream] = in->fs;
@@ -215,7 +197,8 @@ int AspNsxBatch_SetStream(AspNsxBatch* b, void* hip_stream) {
 
 int AspNsxBatch_Synchronize(AspNsxBatch* b) {
   if (!b) return ASP_ERR_PARAM;
-  NSX_TRY(hipSetDevice(b->device));
+  AspDeviceScope dev_scope_;
+  NSX_TRY(dev_scope_.select(b->device));
   NSX_TRY(hipStreamSynchronize(b->stream));
   return ASP_OK;
 }

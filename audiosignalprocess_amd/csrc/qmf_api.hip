@@ -3,7 +3,7 @@
 // caller-owned states.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include "device_scope.h"
+#include "api_common.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -26,22 +26,8 @@ hipError_t launch_synthesis_pair(int32_t* state0, const int16_t* low0, const int
                                  int num_channels, int band_length, hipStream_t s);
 }  // namespace aspqmf
 
-namespace {
-thread_local char g_qmf_err[512] = "";
-int qmf_fail(int code, const char* what, hipError_t e = hipSuccess) {
-  if (e != hipSuccess)
-    snprintf(g_qmf_err, sizeof g_qmf_err, "%s: %s", what, hipGetErrorString(e));
-  else
-    snprintf(g_qmf_err, sizeof g_qmf_err, "%s", what);
-  fprintf(stderr, "asp_split: %s\n", g_qmf_err);
-  return code;
-}
-#define QMF_TRY(expr)                                             \
-  do {                                                            \
-    hipError_t e_ = (expr);                                       \
-    if (e_ != hipSuccess) return qmf_fail(ASP_ERR_HIP, #expr, e_); \
-  } while (0)
-}  // namespace
+#define qmf_fail(...) asp_fail("asp_split", __VA_ARGS__)
+#define QMF_TRY(x) ASP_TRY("asp_split", x)
 
 struct AspQmfBatch {
   int C = 0, device = 0;
@@ -56,11 +42,7 @@ int AspQmfBatch_Create(AspQmfBatch** out, int num_channels, int device) {
   AspDeviceScope dev_scope_;
   if (!out || num_channels <= 0) return qmf_fail(ASP_ERR_PARAM, "AspQmfBatch_Create: bad argument");
   *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return qmf_fail(ASP_ERR_NO_DEVICE, "no HIP device: the band split has no CPU fallback");
-  if (device < 0 || device >= count) return qmf_fail(ASP_ERR_PARAM, "device ordinal out of range");
-  QMF_TRY(hipSetDevice(device));
+  if (int rc = dev_scope_.select("asp_split", device, ASP_ERR_PARAM, "no HIP device: the band split has no CPU fallback")) return rc;
   AspQmfBatch* b = new AspQmfBatch();
   b->C = num_channels;
   b->device = device;
@@ -82,7 +64,7 @@ int AspQmfBatch_Create(AspQmfBatch** out, int num_channels, int device) {
 int AspQmfBatch_Free(AspQmfBatch* b) {
   AspDeviceScope dev_scope_;
   if (!b) return -1;
-  (void)hipSetDevice(b->device);
+  (void)dev_scope_.select(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->state) (void)hipFree(b->state);
   if (b->s_in) (void)hipFree(b->s_in);
@@ -98,7 +80,7 @@ int AspQmfBatch_num_channels(const AspQmfBatch* b) { return b ? b->C : 0; }
 int AspQmfBatch_Reset(AspQmfBatch* b) {
   AspDeviceScope dev_scope_;
   if (!b) return qmf_fail(ASP_ERR_PARAM, "null batch handle");
-  QMF_TRY(hipSetDevice(b->device));
+  QMF_TRY(dev_scope_.select(b->device));
   QMF_TRY(hipMemsetAsync(b->state, 0, (size_t)b->C * 24 * sizeof(int32_t), b->stream));
   return ASP_OK;
 }
@@ -108,7 +90,7 @@ int AspQmfBatch_Analysis(AspQmfBatch* b, const int16_t* in, int band_length, int
   AspDeviceScope dev_scope_;
   if (!b || !in || !low || !high || band_length <= 0 || band_length > ASP_QMF_MAX_BAND)
     return qmf_fail(ASP_ERR_PARAM, "AspQmfBatch_Analysis: bad argument");
-  QMF_TRY(hipSetDevice(b->device));
+  QMF_TRY(dev_scope_.select(b->device));
   const size_t nb = (size_t)b->C * band_length * sizeof(int16_t);
   const int16_t* din = in;
   int16_t *dl = low, *dh = high;
@@ -134,7 +116,7 @@ int AspQmfBatch_Synthesis(AspQmfBatch* b, const int16_t* low, const int16_t* hig
   AspDeviceScope dev_scope_;
   if (!b || !out || !low || !high || band_length <= 0 || band_length > ASP_QMF_MAX_BAND)
     return qmf_fail(ASP_ERR_PARAM, "AspQmfBatch_Synthesis: bad argument");
-  QMF_TRY(hipSetDevice(b->device));
+  QMF_TRY(dev_scope_.select(b->device));
   const size_t nb = (size_t)b->C * band_length * sizeof(int16_t);
   const int16_t *dl = low, *dh = high;
   int16_t* dout = out;
@@ -158,7 +140,7 @@ int AspQmfBatch_Synthesis(AspQmfBatch* b, const int16_t* low, const int16_t* hig
 int AspQmfBatch_ExportState(AspQmfBatch* b, int channel, AspQmfState* out) {
   AspDeviceScope dev_scope_;
   if (!b || !out || channel < 0 || channel >= b->C) return qmf_fail(ASP_ERR_PARAM, "ExportState: bad argument");
-  QMF_TRY(hipSetDevice(b->device));
+  QMF_TRY(dev_scope_.select(b->device));
   QMF_TRY(hipStreamSynchronize(b->stream));
   QMF_TRY(hipMemcpy(out, b->state + (size_t)channel * 24, sizeof *out, hipMemcpyDeviceToHost));
   return ASP_OK;
@@ -167,7 +149,7 @@ int AspQmfBatch_ExportState(AspQmfBatch* b, int channel, AspQmfState* out) {
 int AspQmfBatch_ImportState(AspQmfBatch* b, int channel, const AspQmfState* in) {
   AspDeviceScope dev_scope_;
   if (!b || !in || channel < 0 || channel >= b->C) return qmf_fail(ASP_ERR_PARAM, "ImportState: bad argument");
-  QMF_TRY(hipSetDevice(b->device));
+  QMF_TRY(dev_scope_.select(b->device));
   QMF_TRY(hipStreamSynchronize(b->stream));
   QMF_TRY(hipMemcpy(b->state + (size_t)channel * 24, in, sizeof *in, hipMemcpyHostToDevice));
   return ASP_OK;
@@ -176,7 +158,7 @@ int AspQmfBatch_ImportState(AspQmfBatch* b, int channel, const AspQmfState* in) 
 int AspQmfBatch_Synchronize(AspQmfBatch* b) {
   AspDeviceScope dev_scope_;
   if (!b) return qmf_fail(ASP_ERR_PARAM, "null batch handle");
-  QMF_TRY(hipSetDevice(b->device));
+  QMF_TRY(dev_scope_.select(b->device));
   QMF_TRY(hipStreamSynchronize(b->stream));
   return ASP_OK;
 }
@@ -244,11 +226,7 @@ int AspSplitBatch_Create(AspSplitBatch** out, int num_channels, int num_bands, i
   if (!out || num_channels <= 0 || (num_bands != 2 && num_bands != 3))
     return qmf_fail(ASP_ERR_PARAM, "AspSplitBatch_Create: bad argument");
   *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return qmf_fail(ASP_ERR_NO_DEVICE, "no HIP device: the band split has no CPU fallback");
-  if (device < 0 || device >= count) return qmf_fail(ASP_ERR_PARAM, "device ordinal out of range");
-  QMF_TRY(hipSetDevice(device));
+  if (int rc = dev_scope_.select("asp_split", device, ASP_ERR_PARAM, "no HIP device: the band split has no CPU fallback")) return rc;
   AspSplitBatch* b = new AspSplitBatch();
   b->C = num_channels;
   b->nb = num_bands;
@@ -283,7 +261,7 @@ int AspSplitBatch_Create(AspSplitBatch** out, int num_channels, int num_bands, i
 int AspSplitBatch_Free(AspSplitBatch* b) {
   AspDeviceScope dev_scope_;
   if (!b) return -1;
-  (void)hipSetDevice(b->device);
+  (void)dev_scope_.select(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->up) AspSincBatch_Free(b->up);
   if (b->down) AspSincBatch_Free(b->down);
@@ -302,7 +280,7 @@ int AspSplitBatch_Free(AspSplitBatch* b) {
 int AspSplitBatch_Analysis(AspSplitBatch* b, const int16_t* in, int16_t* bands, int mem) {
   AspDeviceScope dev_scope_;
   if (!b || !in || !bands) return qmf_fail(ASP_ERR_PARAM, "AspSplitBatch_Analysis: bad argument");
-  QMF_TRY(hipSetDevice(b->device));
+  QMF_TRY(dev_scope_.select(b->device));
   const size_t c = (size_t)b->C, total = c * 160 * b->nb * sizeof(int16_t);
   const int16_t* din = in;
   int16_t* dbands = bands;
@@ -335,7 +313,7 @@ int AspSplitBatch_Analysis(AspSplitBatch* b, const int16_t* in, int16_t* bands, 
 int AspSplitBatch_Synthesis(AspSplitBatch* b, const int16_t* bands, int16_t* out, int mem) {
   AspDeviceScope dev_scope_;
   if (!b || !out || !bands) return qmf_fail(ASP_ERR_PARAM, "AspSplitBatch_Synthesis: bad argument");
-  QMF_TRY(hipSetDevice(b->device));
+  QMF_TRY(dev_scope_.select(b->device));
   const size_t c = (size_t)b->C, total = c * 160 * b->nb * sizeof(int16_t);
   const int16_t* dbands = bands;
   int16_t* dout = out;

@@ -3,7 +3,7 @@
 // (doubles, exactly the reference's recurrence), and the batch handle.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include "device_scope.h"
+#include "api_common.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -23,22 +23,8 @@ hipError_t launch_sinc(float* state, const float* kernel_table, const OutDesc* d
                        int src_frames, int dst_frames, const SincPlan& plan, hipStream_t s);
 }
 
-namespace {
-thread_local char g_sinc_err[512] = "";
-int sinc_fail(int code, const char* what, hipError_t e = hipSuccess) {
-  if (e != hipSuccess)
-    snprintf(g_sinc_err, sizeof g_sinc_err, "%s: %s", what, hipGetErrorString(e));
-  else
-    snprintf(g_sinc_err, sizeof g_sinc_err, "%s", what);
-  fprintf(stderr, "asp_resample: %s\n", g_sinc_err);
-  return code;
-}
-#define SINC_TRY(expr)                                             \
-  do {                                                             \
-    hipError_t e_ = (expr);                                        \
-    if (e_ != hipSuccess) return sinc_fail(ASP_ERR_HIP, #expr, e_); \
-  } while (0)
-}  // namespace
+#define sinc_fail(...) asp_fail("asp_resample", __VA_ARGS__)
+#define SINC_TRY(x) ASP_TRY("asp_resample", x)
 
 struct AspSincBatch {
   int C = 0, device = 0, src = 0, dst = 0, buf_len = 0;
@@ -160,11 +146,7 @@ int AspSincBatch_Create(AspSincBatch** out, int num_channels, int source_frames,
   if (!out || num_channels <= 0 || source_frames <= kKernelSize || destination_frames <= 0)
     return sinc_fail(ASP_ERR_PARAM, "AspSincBatch_Create: bad argument");
   *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return sinc_fail(ASP_ERR_NO_DEVICE, "no HIP device: the resampler has no CPU fallback");
-  if (device < 0 || device >= count) return sinc_fail(ASP_ERR_PARAM, "device ordinal out of range");
-  SINC_TRY(hipSetDevice(device));
+  if (int rc = dev_scope_.select("asp_resample", device, ASP_ERR_PARAM, "no HIP device: the resampler has no CPU fallback")) return rc;
   AspSincBatch* b = new AspSincBatch();
   b->C = num_channels;
   b->device = device;
@@ -203,7 +185,7 @@ int AspSincBatch_Create(AspSincBatch** out, int num_channels, int source_frames,
 int AspSincBatch_Free(AspSincBatch* b) {
   AspDeviceScope dev_scope_;
   if (!b) return -1;
-  (void)hipSetDevice(b->device);
+  (void)dev_scope_.select(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->state) (void)hipFree(b->state);
   if (b->ktable) (void)hipFree(b->ktable);
@@ -221,7 +203,7 @@ int AspSincBatch_Free(AspSincBatch* b) {
 int AspSincBatch_SetStream(AspSincBatch* b, void* hip_stream) {
   AspDeviceScope dev_scope_;
   if (!b) return sinc_fail(ASP_ERR_PARAM, "null batch handle");
-  SINC_TRY(hipSetDevice(b->device));
+  SINC_TRY(dev_scope_.select(b->device));
   SINC_TRY(hipStreamSynchronize(b->stream));
   b->stream = hip_stream ? (hipStream_t)hip_stream : b->own_stream;
   return ASP_OK;
@@ -232,7 +214,7 @@ int AspSincBatch_num_channels(const AspSincBatch* b) { return b ? b->C : 0; }
 int AspSincBatch_Resample(AspSincBatch* b, const int16_t* in, int16_t* out, int mem) {
   AspDeviceScope dev_scope_;
   if (!b || !in || !out) return sinc_fail(ASP_ERR_PARAM, "AspSincBatch_Resample: bad argument");
-  SINC_TRY(hipSetDevice(b->device));
+  SINC_TRY(dev_scope_.select(b->device));
   // PushSincResampler::Resample (push_sinc_resampler.cc:47-60): a priming pass on the first call
   SincPlan plan;
   memset(&plan, 0, sizeof plan);
@@ -277,7 +259,7 @@ int AspSincBatch_Resample(AspSincBatch* b, const int16_t* in, int16_t* out, int 
 int AspSincBatch_Synchronize(AspSincBatch* b) {
   AspDeviceScope dev_scope_;
   if (!b) return sinc_fail(ASP_ERR_PARAM, "null batch handle");
-  SINC_TRY(hipSetDevice(b->device));
+  SINC_TRY(dev_scope_.select(b->device));
   SINC_TRY(hipStreamSynchronize(b->stream));
   return ASP_OK;
 }

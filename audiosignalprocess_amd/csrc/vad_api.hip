@@ -3,7 +3,7 @@
 // No CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include "device_scope.h"
+#include "api_common.h"
 
 #include <stdio.h>
 #include <string.h>
@@ -20,41 +20,15 @@ hipError_t launch_gaussian(const int16_t* in, const int16_t* mean, const int16_t
                            int16_t* delta, hipStream_t st);
 }  // namespace aspvad
 
-namespace {
-thread_local char g_vad_err[512] = "";
-int vad_fail(int code, const char* what, hipError_t e = hipSuccess) {
-  if (e != hipSuccess)
-    snprintf(g_vad_err, sizeof g_vad_err, "%s: %s", what, hipGetErrorString(e));
-  else
-    snprintf(g_vad_err, sizeof g_vad_err, "%s", what);
-  fprintf(stderr, "asp_vad: %s\n", g_vad_err);
-  return code;
-}
-#define VAD_TRY(expr)                                             \
-  do {                                                            \
-    hipError_t e_ = (expr);                                       \
-    if (e_ != hipSuccess) return vad_fail(ASP_ERR_HIP, #expr, e_); \
-  } while (0)
-
-// grows a device buffer to at least `bytes`
-hipError_t reserve(void** p, size_t* cap, size_t bytes) {
-  if (*cap >= bytes) return hipSuccess;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipSuccess) *cap = bytes;
-  return e;
-}
-}  // namespace
+#define vad_fail(...) asp_fail("asp_vad", __VA_ARGS__)
+#define VAD_TRY(x) ASP_TRY("asp_vad", x)
 
 struct AspVadBatch {
   int S = 0, device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
   AspVadState* state = nullptr;          // [S]
   std::vector<unsigned char> inited;     // host mirror of init_flag == 42, per stream
-  void *s_in = nullptr, *s_dec = nullptr, *s_lev = nullptr;   // staging for host-memory callers
-  size_t c_in = 0, c_dec = 0, c_lev = 0;
+  AspStage s_in, s_dec, s_lev;           // staging for host-memory callers
 };
 
 extern "C" {
@@ -70,11 +44,7 @@ int AspVadBatch_Create(AspVadBatch** out, int num_streams, int device) {
   AspDeviceScope dev_scope_;
   if (!out || num_streams <= 0) return vad_fail(ASP_ERR_PARAM, "AspVadBatch_Create: bad argument");
   *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return vad_fail(ASP_ERR_NO_DEVICE, "no HIP device: the VAD has no CPU fallback");
-  if (device < 0 || device >= count) return vad_fail(ASP_ERR_PARAM, "device ordinal out of range");
-  VAD_TRY(hipSetDevice(device));
+  if (int rc = dev_scope_.select("asp_vad", device, ASP_ERR_PARAM, "no HIP device: the VAD has no CPU fallback")) return rc;
   AspVadBatch* b = new AspVadBatch();
   b->S = num_streams;
   b->device = device;
@@ -96,12 +66,12 @@ int AspVadBatch_Create(AspVadBatch** out, int num_streams, int device) {
 int AspVadBatch_Free(AspVadBatch* b) {
   AspDeviceScope dev_scope_;
   if (!b) return ASP_ERR_PARAM;
-  (void)hipSetDevice(b->device);
+  (void)dev_scope_.select(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->state) (void)hipFree(b->state);
-  if (b->s_in) (void)hipFree(b->s_in);
-  if (b->s_dec) (void)hipFree(b->s_dec);
-  if (b->s_lev) (void)hipFree(b->s_lev);
+  b->s_in.release();
+  b->s_dec.release();
+  b->s_lev.release();
   if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
   delete b;
   return ASP_OK;
@@ -111,7 +81,7 @@ int AspVadBatch_num_streams(const AspVadBatch* b) { return b ? b->S : 0; }
 
 static int init_range(AspVadBatch* b, int first, int count, int init, int mode) {
   AspDeviceScope dev_scope_;
-  VAD_TRY(hipSetDevice(b->device));
+  VAD_TRY(dev_scope_.select(b->device));
   VAD_TRY(aspvad::launch_init(b->state, first, count, init, mode, b->stream));
   if (init) memset(b->inited.data() + first, 1, (size_t)count);
   return ASP_OK;
@@ -149,20 +119,20 @@ int AspVadBatch_Process(AspVadBatch* b, int fs, int frame_length, const int16_t*
     return vad_fail(ASP_ERR_PARAM, "AspVadBatch_Process: invalid rate / frame length");
   for (int s = 0; s < b->S; ++s)
     if (!b->inited[s]) return vad_fail(ASP_ERR_STATE, "AspVadBatch_Process: stream not initialised");
-  VAD_TRY(hipSetDevice(b->device));
+  VAD_TRY(dev_scope_.select(b->device));
   const size_t n = (size_t)num_frames * b->S;
   const size_t in_bytes = n * frame_length * sizeof(int16_t);
   const int16_t* din = in;
   int8_t* ddec = decisions;
   int32_t* dlev = levels;
   if (mem == ASP_MEM_HOST) {
-    VAD_TRY(reserve(&b->s_in, &b->c_in, in_bytes));
-    VAD_TRY(reserve(&b->s_dec, &b->c_dec, n));
-    if (levels) VAD_TRY(reserve(&b->s_lev, &b->c_lev, n * sizeof(int32_t)));
-    VAD_TRY(hipMemcpyAsync(b->s_in, in, in_bytes, hipMemcpyHostToDevice, b->stream));
-    din = (const int16_t*)b->s_in;
-    ddec = (int8_t*)b->s_dec;
-    dlev = levels ? (int32_t*)b->s_lev : nullptr;
+    VAD_TRY(b->s_in.reserve(in_bytes));
+    VAD_TRY(b->s_dec.reserve(n));
+    if (levels) VAD_TRY(b->s_lev.reserve(n * sizeof(int32_t)));
+    VAD_TRY(hipMemcpyAsync(b->s_in.p, in, in_bytes, hipMemcpyHostToDevice, b->stream));
+    din = (const int16_t*)b->s_in.p;
+    ddec = (int8_t*)b->s_dec.p;
+    dlev = levels ? (int32_t*)b->s_lev.p : nullptr;
   } else if (mem != ASP_MEM_DEVICE) {
     return vad_fail(ASP_ERR_PARAM, "mem must be ASP_MEM_HOST or ASP_MEM_DEVICE");
   } else if (((uintptr_t)in & 3) != 0) {
@@ -181,16 +151,16 @@ int AspVadBatch_Features(AspVadBatch* b, const int16_t* in, int frame_length, in
   AspDeviceScope dev_scope_;
   if (!b || !in || !features || WebRtcVad_ValidRateAndFrameLength(8000, frame_length) != 0)
     return vad_fail(ASP_ERR_PARAM, "AspVadBatch_Features: bad argument");
-  VAD_TRY(hipSetDevice(b->device));
+  VAD_TRY(dev_scope_.select(b->device));
   const size_t in_bytes = (size_t)b->S * frame_length * sizeof(int16_t), out_bytes = (size_t)b->S * 7 * sizeof(int16_t);
   const int16_t* din = in;
   int16_t* dout = features;
   if (mem == ASP_MEM_HOST) {
-    VAD_TRY(reserve(&b->s_in, &b->c_in, in_bytes));
-    VAD_TRY(reserve(&b->s_lev, &b->c_lev, out_bytes));
-    VAD_TRY(hipMemcpyAsync(b->s_in, in, in_bytes, hipMemcpyHostToDevice, b->stream));
-    din = (const int16_t*)b->s_in;
-    dout = (int16_t*)b->s_lev;
+    VAD_TRY(b->s_in.reserve(in_bytes));
+    VAD_TRY(b->s_lev.reserve(out_bytes));
+    VAD_TRY(hipMemcpyAsync(b->s_in.p, in, in_bytes, hipMemcpyHostToDevice, b->stream));
+    din = (const int16_t*)b->s_in.p;
+    dout = (int16_t*)b->s_lev.p;
   } else if (mem != ASP_MEM_DEVICE || ((uintptr_t)in & 3) != 0) {
     return vad_fail(ASP_ERR_PARAM, "AspVadBatch_Features: bad memory argument");
   }
@@ -205,7 +175,7 @@ int AspVadBatch_Features(AspVadBatch* b, const int16_t* in, int frame_length, in
 int AspVadBatch_ExportState(AspVadBatch* b, int stream, AspVadState* out) {
   AspDeviceScope dev_scope_;
   if (!b || !out || stream < 0 || stream >= b->S) return vad_fail(ASP_ERR_PARAM, "ExportState: bad argument");
-  VAD_TRY(hipSetDevice(b->device));
+  VAD_TRY(dev_scope_.select(b->device));
   VAD_TRY(hipMemcpyAsync(out, b->state + stream, sizeof *out, hipMemcpyDeviceToHost, b->stream));
   VAD_TRY(hipStreamSynchronize(b->stream));
   return ASP_OK;
@@ -214,7 +184,7 @@ int AspVadBatch_ExportState(AspVadBatch* b, int stream, AspVadState* out) {
 int AspVadBatch_ImportState(AspVadBatch* b, int stream, const AspVadState* in) {
   AspDeviceScope dev_scope_;
   if (!b || !in || stream < 0 || stream >= b->S) return vad_fail(ASP_ERR_PARAM, "ImportState: bad argument");
-  VAD_TRY(hipSetDevice(b->device));
+  VAD_TRY(dev_scope_.select(b->device));
   VAD_TRY(hipMemcpyAsync(b->state + stream, in, sizeof *in, hipMemcpyHostToDevice, b->stream));
   VAD_TRY(hipStreamSynchronize(b->stream));
   b->inited[stream] = in->init_flag == aspvad::kInitCheck;
@@ -224,7 +194,7 @@ int AspVadBatch_ImportState(AspVadBatch* b, int stream, const AspVadState* in) {
 int AspVadBatch_SetStream(AspVadBatch* b, void* hip_stream) {
   AspDeviceScope dev_scope_;
   if (!b) return vad_fail(ASP_ERR_PARAM, "null batch handle");
-  VAD_TRY(hipSetDevice(b->device));
+  VAD_TRY(dev_scope_.select(b->device));
   VAD_TRY(hipStreamSynchronize(b->stream));
   b->stream = hip_stream ? (hipStream_t)hip_stream : b->own_stream;
   return ASP_OK;
@@ -233,7 +203,7 @@ int AspVadBatch_SetStream(AspVadBatch* b, void* hip_stream) {
 int AspVadBatch_Synchronize(AspVadBatch* b) {
   AspDeviceScope dev_scope_;
   if (!b) return vad_fail(ASP_ERR_PARAM, "null batch handle");
-  VAD_TRY(hipSetDevice(b->device));
+  VAD_TRY(dev_scope_.select(b->device));
   VAD_TRY(hipStreamSynchronize(b->stream));
   return ASP_OK;
 }
@@ -243,10 +213,7 @@ int AspVad_debug_gaussian(const int16_t* input, const int16_t* mean, const int16
   AspDeviceScope dev_scope_;
   if (!input || !mean || !std_ || !probability || !delta || n <= 0)
     return vad_fail(ASP_ERR_PARAM, "AspVad_debug_gaussian: bad argument");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count)
-    return vad_fail(ASP_ERR_NO_DEVICE, "no HIP device");
-  VAD_TRY(hipSetDevice(device));
+  if (int rc = dev_scope_.select("asp_vad", device, ASP_ERR_NO_DEVICE, "no HIP device")) return rc;
   int16_t* d = nullptr;
   const size_t b16 = (size_t)n * sizeof(int16_t);
   VAD_TRY(hipMalloc((void**)&d, 4 * b16 + (size_t)n * sizeof(int32_t)));

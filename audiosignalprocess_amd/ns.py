@@ -22,6 +22,16 @@ class AspError(RuntimeError):
     pass
 
 
+def _declare(lib, sig):
+    """Sets the argument types of the entry points in `sig` (name -> argtypes); every one returns int."""
+    for name, args in sig.items():
+        if os.environ.get("ASP_AMD_LIB") and not hasattr(lib, name):
+            continue  # an earlier build of the library loaded for a same-box A / B run (build.py)
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = C.c_int
+
+
 def load_library():
     """dlopen lib/libasp_amd.so (built by build.py / __graft_entry__.build)."""
     global _lib
@@ -77,12 +87,7 @@ def load_library():
         "AspNs_rdft128_batch": [vp, ip, ip, ip, ip],
         "AspNs_device_count": [],
     }
-    for name, args in sig.items():
-        if os.environ.get("ASP_AMD_LIB") and not hasattr(lib, name):
-            continue  # an earlier build of the library loaded for a same-box A / B run (build.py)
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = C.c_int
+    _declare(lib, sig)
     lib.AspNsBatch_GetStream.argtypes = [vp]
     lib.AspNsBatch_GetStream.restype = vp
     lib.AspNs_last_error.restype = C.c_char_p
@@ -91,6 +96,7 @@ def load_library():
 
 
 def _check(rc, what):
+    """Raises AspError with the calling thread's last failure text (any module's: AspNs_last_error is library-wide)."""
     if rc != 0:
         raise AspError("%s failed (%d): %s" % (what, rc, load_library().AspNs_last_error().decode()))
 

@@ -8,7 +8,7 @@ import numpy as np
 
 from ._abi import MEM_DEVICE, MEM_HOST  # noqa: F401
 from .build import LIBDIR
-from .ns import AspError, device_count, load_library as _load  # noqa: F401
+from .ns import AspError, _check, _declare, device_count, load_library as _load  # noqa: F401
 
 I16, U16, I32, U32 = C.c_int16, C.c_uint16, C.c_int32, C.c_uint32
 # NoiseSuppressionFixedC without its pointers, in its order: (name, ctype, count)
@@ -72,10 +72,7 @@ def load_library():
             "WebRtcNsx_Process": [vp, vp, ip, vp],
             "AspNsx_last_refused": [],
         }
-        for name, args in sig.items():
-            fn = getattr(lib, name)
-            fn.argtypes = args
-            fn.restype = ip
+        _declare(lib, sig)
         lib.WebRtcNsx_Process.restype = None
         lib.AspNsx_state_size.argtypes = []
         lib.AspNsx_state_size.restype = C.c_size_t
@@ -97,9 +94,7 @@ class NsxBatch:
     def __init__(self, num_streams, device=0):
         self.lib = load_library()
         self.h = C.c_void_p()
-        rc = self.lib.AspNsxBatch_Create(C.byref(self.h), num_streams, device)
-        if rc != 0:
-            raise AspError("AspNsxBatch_Create", rc)
+        _check(self.lib.AspNsxBatch_Create(C.byref(self.h), num_streams, device), "AspNsxBatch_Create")
         self.S = num_streams
 
     def close(self):
@@ -123,9 +118,8 @@ class NsxBatch:
         low = np.ascontiguousarray(x[:, 0])
         high = np.ascontiguousarray(x[:, 1:]) if nb > 1 else None
         lo, ho = (low, high) if out is x else (np.zeros_like(low), None if high is None else np.zeros_like(high))
-        rc = self.lib.AspNsxBatch_ProcessFrames(self.h, F, _ptr(low), _ptr(high), _ptr(lo), _ptr(ho), nb, n, MEM_HOST)
-        if rc != 0:
-            raise AspError("AspNsxBatch_ProcessFrames", rc)
+        _check(self.lib.AspNsxBatch_ProcessFrames(self.h, F, _ptr(low), _ptr(high), _ptr(lo), _ptr(ho), nb, n, MEM_HOST),
+               "AspNsxBatch_ProcessFrames")
         y = np.empty_like(x)
         y[:, 0] = lo
         if nb > 1:
@@ -134,9 +128,7 @@ class NsxBatch:
 
     def export_state(self, stream):
         st = AspNsxState()
-        rc = self.lib.AspNsxBatch_ExportState(self.h, stream, C.addressof(st))
-        if rc != 0:
-            raise AspError("AspNsxBatch_ExportState", rc)
+        _check(self.lib.AspNsxBatch_ExportState(self.h, stream, C.addressof(st)), "AspNsxBatch_ExportState")
         return st
 
     def import_state(self, stream, st):

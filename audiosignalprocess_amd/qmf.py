@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._abi import MEM_DEVICE, MEM_HOST
-from .ns import AspError, load_library
+from .ns import AspError, _check, _declare, load_library  # noqa: F401
 
 _sig_done = False
 
@@ -33,17 +33,9 @@ def _lib():
             "AspQmfBatch_ImportState": [vp, ip, C.POINTER(AspQmfState)],
             "AspQmfBatch_Synchronize": [vp],
         }
-        for name, args in sig.items():
-            fn = getattr(lib, name)
-            fn.argtypes = args
-            fn.restype = C.c_int
+        _declare(lib, sig)
         _sig_done = True
     return lib
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise AspError("%s failed (%d)" % (what, rc))
 
 
 class QmfBatch:

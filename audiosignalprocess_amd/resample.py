@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._abi import MEM_HOST
-from .ns import AspError, load_library
+from .ns import _check, _declare, load_library
 
 _sig_done = False
 
@@ -23,10 +23,7 @@ def _lib():
             "AspSincBatch_Synchronize": [vp],
             "AspSincBatch_kernel_table": [vp, vp, ip],
         }
-        for name, args in sig.items():
-            fn = getattr(lib, name)
-            fn.argtypes = args
-            fn.restype = C.c_int
+        _declare(lib, sig)
         _sig_done = True
     return lib
 
@@ -38,18 +35,14 @@ class SincBatch:
         self.lib = _lib()
         self.C, self.src, self.dst = int(num_channels), int(src_frames), int(dst_frames)
         h = C.c_void_p()
-        rc = self.lib.AspSincBatch_Create(C.byref(h), self.C, self.src, self.dst, device)
-        if rc != 0:
-            raise AspError("AspSincBatch_Create failed (%d)" % rc)
+        _check(self.lib.AspSincBatch_Create(C.byref(h), self.C, self.src, self.dst, device), "AspSincBatch_Create")
         self.h = h
 
     def resample(self, x):
         x = np.ascontiguousarray(x, np.int16)
         assert x.shape == (self.C, self.src)
         out = np.empty((self.C, self.dst), np.int16)
-        rc = self.lib.AspSincBatch_Resample(self.h, x.ctypes.data, out.ctypes.data, MEM_HOST)
-        if rc != 0:
-            raise AspError("AspSincBatch_Resample failed (%d)" % rc)
+        _check(self.lib.AspSincBatch_Resample(self.h, x.ctypes.data, out.ctypes.data, MEM_HOST), "AspSincBatch_Resample")
         return out
 
     def kernel_table(self):

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._abi import MEM_DEVICE, MEM_HOST
-from .ns import AspError, load_library
+from .ns import AspError, _check, _declare, load_library  # noqa: F401
 
 _sig_done = False
 
@@ -51,19 +51,11 @@ def _lib():
             "WebRtcVad_Process": [vp, ip, vp, ip],
             "WebRtcVad_ValidRateAndFrameLength": [ip, ip],
         }
-        for name, args in sig.items():
-            fn = getattr(lib, name)
-            fn.argtypes = args
-            fn.restype = C.c_int
+        _declare(lib, sig)
         lib.WebRtcVad_Free.argtypes = [vp]
         lib.WebRtcVad_Free.restype = None
         _sig_done = True
     return lib
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise AspError("%s failed (%d)" % (what, rc))
 
 
 class VadBatch:

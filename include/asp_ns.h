@@ -115,7 +115,8 @@ enum {
   ASP_OK = 0,
   ASP_ERR_PARAM = -1,    /* bad argument (same value the reference returns)   */
   ASP_ERR_NO_DEVICE = -2,/* no usable HIP device / kernel image not loadable  */
-  ASP_ERR_HIP = -3,      /* a HIP call failed (see AspNs_last_error)          */
+  ASP_ERR_HIP = -3,      /* a HIP call failed (AspNs_last_error has the text,
+                            whichever module of the library failed)          */
   ASP_ERR_STATE = -4     /* handle not initialised                            */
 };
 
@@ -236,7 +237,8 @@ int AspNsBatch_LastEnqueueUs(AspNsBatch* b, double* us);
 
 /* Number of HIP devices visible, or a negative error code. */
 int AspNs_device_count(void);
-/* Text of the most recent error on this thread ("" if none). */
+/* Text of the most recent failure on this thread ("" if none).  The record is library-wide: a failure
+   of any module (NS, BT, AEC, split, resample, VAD, AECM, NSX) overwrites it. */
 const char* AspNs_last_error(void);
 
 /* Host copy of the constant tables the kernels use (layout: struct NsTables in

@@ -19,7 +19,8 @@ def declared_functions(header):
     return sorted(names - {"_Static_assert"})
 
 
-@pytest.mark.parametrize("header", ["asp_ns.h", "wav_io.h", "asp_bt.h", "asp_aec.h", "asp_split.h", "asp_resample.h"])
+@pytest.mark.parametrize("header", ["asp_ns.h", "wav_io.h", "asp_bt.h", "asp_aec.h", "asp_split.h", "asp_resample.h",
+                                    "asp_vad.h", "asp_aecm.h", "asp_nsx.h"])
 def test_every_declared_symbol_is_exported(built_lib, header):
     lib = C.CDLL(built_lib)
     names = declared_functions(header)
@@ -89,9 +90,27 @@ def test_no_device_fails_loudly(built_lib):
     assert lib.WebRtcNs_Create(C.byref(h)) == -1
     from audiosignalprocess_amd import aec
 
-    with pytest.raises(ns.AspError):
+    with pytest.raises(ns.AspError) as exc:
         aec.AecBatch(2)
+    assert "no HIP device" in str(exc.value)      # the failing module's own text, through the library-wide record
     assert lib.WebRtcAec_Create(C.byref(h)) == -1
+
+
+def test_last_error_is_library_wide(built_lib):
+    """AspNs_last_error returns the calling thread's last failure text from any module, and the Python mirrors put it
+    into their AspError.  Both refusals happen before a device is looked at, so this runs with or without a GPU."""
+    from audiosignalprocess_amd import bt, ns, vad
+
+    lib = ns.load_library()
+    with pytest.raises(ns.AspError) as exc:
+        bt.BtBatch(1, 7)                          # AspBtBatch_Create: "win_size must be even, ..."
+    assert "win_size" in lib.AspNs_last_error().decode()
+    assert str(exc.value).startswith("AspBtBatch_Create failed (-1)") and "win_size" in str(exc.value)
+    with pytest.raises(ns.AspError) as exc:
+        vad.VadBatch(0)                           # AspVadBatch_Create: num_streams = 0
+    text = lib.AspNs_last_error().decode()
+    assert "AspVadBatch_Create: bad argument" in text and "win_size" not in text    # overwritten, not appended
+    assert "AspVadBatch_Create: bad argument" in str(exc.value)
 
 
 def test_wav_io_roundtrip(built_lib, tmp_path):

@@ -166,3 +166,63 @@ def test_two_shards_on_two_devices_aec_and_bt_vs_oracle():
         for ch in range(n):
             assert np.array_equal(y[ch].view(np.uint32), OracleBt(1024).run(x[ch]).view(np.uint32))
         assert torch.cuda.current_device() == 0
+
+
+@pytest.mark.gpu
+def test_second_device_vad_aecm_nsx_split_sinc_put_the_device_back():
+    """The `device >= 1` path of VadBatch, AecmBatch, NsxBatch, SplitBatch and SincBatch: the same call on device 1 and
+    on device 0 gives the same bits, and the caller's current device is still 0 after every step (create, run,
+    export-state where the mirror has it, close).  Skipped on a one-GPU box."""
+    import torch
+
+    from audiosignalprocess_amd.aecm import AecmBatch
+    from audiosignalprocess_amd.ns import device_count
+    from audiosignalprocess_amd.nsx import NsxBatch
+    from audiosignalprocess_amd.qmf import SplitBatch
+    from audiosignalprocess_amd.resample import SincBatch
+    from audiosignalprocess_amd.synth import aecm_pair, nsx_frames, vad_frames
+    from audiosignalprocess_amd.vad import VadBatch
+
+    if device_count() < 2:
+        pytest.skip("one HIP device on this box (the 8-GPU curve is the driver's to measure)")
+    torch.cuda.set_device(0)
+    S, F = 3, 6
+    x_vad = vad_frames(S, F, 16000, 10)
+    far, near, clean = aecm_pair(S, F, 160)
+    x_nsx = nsx_frames(S, F, 160, 2)
+    x_split = vad_frames(S, 1, 32000, 10)[0]     # [S][320]
+    x_sinc = vad_frames(S, 1, 48000, 10)[0]      # [S][480]
+
+    def make_aecm(device):
+        return AecmBatch(S, fs=16000, device=device)
+
+    def make_nsx(device):
+        b = NsxBatch(S, device=device)
+        assert b.init(32000) == 0 and torch.cuda.current_device() == 0
+        return b
+
+    # (constructor, run -> list of arrays, state export of stream 0 as bytes or None)
+    cases = [
+        ("vad", lambda d: VadBatch(S, device=d, mode=2), lambda b: list(b.process(16000, x_vad)),
+         lambda b: bytes(b.export_state(0))),
+        ("aecm", make_aecm, lambda b: list(b.process_frames(far, near, clean, 50)), lambda b: bytes(b.export_state(0))),
+        ("nsx", make_nsx, lambda b: [b.process_frames(x_nsx)], lambda b: bytes(b.export_state(0))),
+        ("split", lambda d: SplitBatch(S, 2, device=d), lambda b: [b.analysis(x_split)], None),
+        ("sinc", lambda d: SincBatch(S, 480, 160, device=d), lambda b: [b.resample(x_sinc)], None),
+    ]
+    for name, make, run, export in cases:
+        got = []
+        for device in (1, 0):
+            b = make(device)
+            assert torch.cuda.current_device() == 0, (name, "create", device)
+            out = run(b)
+            assert torch.cuda.current_device() == 0, (name, "run", device)
+            if export is not None:
+                out.append(np.frombuffer(export(b), np.uint8))
+                assert torch.cuda.current_device() == 0, (name, "export_state", device)
+            b.close()
+            assert torch.cuda.current_device() == 0, (name, "close", device)
+            got.append(out)
+        assert len(got[0]) == len(got[1])
+        for a1, a0 in zip(*got):
+            assert a1.shape == a0.shape and a1.tobytes() == a0.tobytes(), name

@@ -13,7 +13,8 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.environ.get("ASP_AMD_LIB") or os.path.join(LIBDIR, "libasp_amd.so")
 SOURCES = ["ns_kernels.hip", "ns_kernels1.hip", "ns_kernels2.hip", "ns_kernels_hb.hip", "ns_api.hip", "bt_kernels.hip", "bt_kernels8.hip", "bt_api.hip",
            "aec_kernels.hip", "aec_delay_kernels.hip", "aec_api.hip", "qmf_kernels.hip", "qmf_api.hip", "sinc_kernels.hip", "sinc_api.hip",
-           "vad_kernels.hip", "vad_api.hip", "aecm_kernels.hip", "aecm_api.hip", "nsx_kernels.hip", "nsx_api.hip"]
+           "vad_kernels.hip", "vad_api.hip", "aecm_kernels.hip", "aecm_api.hip", "nsx_kernels.hip", "nsx_api.hip",
+           "splrs_kernels.hip", "splrs_api.hip"]
 C_SOURCES = ["wav_io.c"]  # host-only C (kept C, as in the reference)
 # -ffp-contract=off: parity with the reference depends on unfused mul/add.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",
@@ -85,8 +86,9 @@ def build_library(force=False, verbose=False):
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)
         objs.append(o)
-    # the CPU builds of the AECM and NSX cores, for the tests only (no CPU path in libasp_amd.so)
-    for src_name, so_name in (("aecm_restate.cpp", "libaecm_restate.so"), ("nsx_restate.cpp", "libnsx_restate.so")):
+    # the CPU builds of the AECM, NSX and resampler cores, for the tests only (no CPU path in libasp_amd.so)
+    for src_name, so_name in (("aecm_restate.cpp", "libaecm_restate.so"), ("nsx_restate.cpp", "libnsx_restate.so"),
+                              ("splrs_restate.cpp", "libsplrs_restate.so")):
         src = os.path.join(CSRC, src_name)
         so = os.path.join(LIBDIR, so_name)
         if force or _stale(so, [src] + hdrs):
@@ -103,32 +105,29 @@ def build_library(force=False, verbose=False):
 
 
 def build_drivers(verbose=False):
-    """The C WAV drivers (drivers/*.c) linked against the in-tree library."""
+    """The C and C++ drivers (drivers/*.c, drivers/*.cpp) linked against the in-tree library."""
     out_dir = os.path.join(ROOT, "drivers", "bin")
     os.makedirs(out_dir, exist_ok=True)
     built = []
-    for name in ["test_ns_module", "ns_batch_wav", "test_aec_module", "bt_main", "test_aecm_module", "test_nsx_module", "test_vad_module"]:
-        src = os.path.join(ROOT, "drivers", name + ".c")
+    # (name, header or None). The .c drivers link the C ABI; the .cpp ones are clients of the header-only classes
+    # APM_NS (include/apm_ns.h) and webrtc::Resampler (include/webrtc_resampler.h). Callers index this list from both
+    # ends (test_ns_module first, test_vad_module and apm_ns_raw last), so new drivers go in the middle.
+    drivers = [("test_ns_module", None), ("ns_batch_wav", None), ("test_aec_module", None), ("bt_main", None),
+               ("test_aecm_module", None), ("test_nsx_module", None), ("test_resampler_module", "webrtc_resampler.h"),
+               ("test_vad_module", None), ("apm_ns_raw", "apm_ns.h")]
+    for name, header in drivers:
+        src = os.path.join(ROOT, "drivers", name + (".cpp" if header else ".c"))
         exe = os.path.join(out_dir, name)
-        if _stale(exe, [src, LIB]):
-            cmd = ["gcc", "-O2", "-std=gnu99", "-Wall", "-I" + os.path.join(ROOT, "include"), src,
-                   "-L" + LIBDIR, "-lasp_amd", "-Wl,-rpath,$ORIGIN/../../audiosignalprocess_amd/lib",
-                   "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
+        deps = [src, LIB] + ([os.path.join(ROOT, "include", header)] if header else [])
+        if _stale(exe, deps):
+            cc = ["g++", "-O2", "-std=c++11"] if header else ["gcc", "-O2", "-std=gnu99"]
+            cmd = cc + ["-Wall", "-I" + os.path.join(ROOT, "include"), src,
+                        "-L" + LIBDIR, "-lasp_amd", "-Wl,-rpath,$ORIGIN/../../audiosignalprocess_amd/lib",
+                        "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
             if verbose:
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)
         built.append(exe)
-    # C++ client of the header-only APM_NS class (include/apm_ns.h)
-    src = os.path.join(ROOT, "drivers", "apm_ns_raw.cpp")
-    exe = os.path.join(out_dir, "apm_ns_raw")
-    if _stale(exe, [src, LIB, os.path.join(ROOT, "include", "apm_ns.h")]):
-        cmd = ["g++", "-O2", "-std=c++11", "-Wall", "-I" + os.path.join(ROOT, "include"), src,
-               "-L" + LIBDIR, "-lasp_amd", "-Wl,-rpath,$ORIGIN/../../audiosignalprocess_amd/lib",
-               "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.run(cmd, check=True)
-    built.append(exe)
     return built
 
 

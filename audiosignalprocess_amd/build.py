@@ -26,7 +26,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++
 # with dependent scalar loads before the first vector load can issue (-0.5 us per NS step, measured);
 # the object carries a prologue for firmware without the feature
 _PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=8"]
-EXTRA = {"ns_kernels.hip": list(_PRELOAD), "ns_kernels1.hip": list(_PRELOAD), "ns_kernels2.hip": list(_PRELOAD),
+EXTRA = {"ns_kernels.hip": list(_PRELOAD),
+         # the hand-off build's step loop: machine LICM hoists the fp64 constants of the whole frame step in front of it
+         # and they spill (60 VGPRs); without it both hand-off instantiations hold 128 VGPRs, no spill, no scratch
+         # (profiles/r05_ns_walk_resource_usage.txt)
+         "ns_kernels1.hip": list(_PRELOAD) + ["-mllvm", "-disable-machine-licm"],
+         "ns_kernels2.hip": list(_PRELOAD),
          # the echo canceller's block is long straight-line code at 4 waves per SIMD: the compiler's ILP-first
          # scheduling measured 92.7-93.8 us per step against 95.5 us in one session (max-ilp: 97-99 us)
          "aec_kernels.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],

@@ -9,6 +9,14 @@
 // a multiple of 8, so that (with workgroups dealt round-robin to the 8 XCDs) both come from the same XCD's
 // in-order share of the grid.
 //
+// The chunked form (ns_kernels1.hip, NsFlowArgs::walk): blockIdx.y is a CHUNK of C consecutive steps, and workgroup
+// (x, c) walks steps c C .. min(steps, (c + 1) C) - 1 of its streams in a loop.  Only the chunk's first step waits
+// (for the wave of chunk c - 1, dispatched earlier: the same argument as above); between two steps of its own the
+// wave drains its stores -- which is also what lets it read them back -- publishes seq[s], and goes on.  seq[s] still
+// counts the steps stream s has completed, after every step.  With C = steps no workgroup waits for another one of
+// the launch (only for the previous launch, which stream order has finished): nothing then rests on dispatch order.
+// C = 1 is the form above.  The host picks C (ns_api.hip, flow_walk).
+//
 // What orders the two is a per-stream step counter in memory, seq[s]:
 //   * the wave that has finished step k of stream s drains every store it issued (handoff_drain:
 //     s_waitcnt vmcnt(0)), then one lane stores seq[s] = k + 1 (handoff_publish);

@@ -31,8 +31,8 @@ hipError_t launch_ns_frame1(bool io16, float* state, int32_t* hist, const NsTabl
                             unsigned long long* stamps = nullptr, int stamp_mode = 0);
 hipError_t launch_ns_frame1_flow(bool io16, float* state, int32_t* hist, const NsTables* T,
                                  const float* in, float* out, int num_streams, hipStream_t s,
-                                 unsigned* seq, unsigned* abort_w, unsigned want, int steps, int slot0, int ring,
-                                 size_t per, unsigned long long* stamps = nullptr);
+                                 unsigned* seq, unsigned* abort_w, unsigned want, int steps, int walk, int slot0,
+                                 int ring, size_t per, unsigned long long* stamps = nullptr);
 hipError_t launch_ns_frame2(bool io16, float* state, int32_t* hist, const NsTables* T,
                             const float* in, float* out, int num_streams, hipStream_t s,
                             unsigned long long* stamps = nullptr);
@@ -590,6 +590,9 @@ struct AspNsBatch {
   // kHandoffMaxSteps consecutive frame steps of a K-step call per launch; a per-stream step counter in memory
   // orders step k + 1 of a stream behind its step k.  -1 = default (on for the pair-layout kernel), 0 = off, 1 = on.
   int flow = -1;
+  // Steps a workgroup of the pair-layout hand-off kernel walks (NsFlowArgs::walk): 0 = auto (kFlowWalkAuto), else forced.
+  int flow_walk = 0;
+  int flow_chunks = 0;  // grid y of the last such launch (AspNsBatch_DebugFlowChunks)
   HandoffSync sync;
   // > 16 kHz: 1 or 2 high bands next to the low band (ns_core.c:1362-1414)
   uint32_t fs = 16000;
@@ -833,8 +836,18 @@ static bool flow_applies(const AspNsBatch* b, int steps) {
   return on && steps >= 2 && b->paired && b->kernel != 1 && b->fs != 8000 && b->timeline == nullptr;
 }
 
+// Steps per workgroup of a pair-layout hand-off launch of m steps.  Auto: kFlowWalkAuto.  Measured at 4096 streams
+// (profiles/r05_ns_walk_ab.txt): 2 and 4 steps 12.10-12.25 us per step, 8 and 16 steps 12.2-12.4 us, against
+// 12.4-12.5 us with one step per workgroup; the whole launch (64 steps, no workgroup waiting for another) 12.8 us --
+// every wave of the chip is in the same phase again, as with one launch per step.  8192 and 6000 streams (a ragged
+// last round) gain the same way.  AspNsBatch_SetFlowWalk / ASP_NS_FLOW_WALK force a length.
+// Why 4 and not 2 (level at 4096 streams, inside the run-to-run spread): 4 pays the set-up half as often and was not
+// behind at any batch size or ring measured.
+constexpr int kFlowWalkAuto = 4;
+
 // K steps of the hand-off build on the batch's stream: launches of up to kHandoffMaxSteps consecutive frame
-// steps each (grid y = step); launches follow each other in stream order.
+// steps each (pair-layout kernel: grid y = chunk of steps, kFlowWalkAuto; kernel 2: grid y = step); launches follow
+// each other in stream order.
 static int flow_steps(AspNsBatch* b, const float* din, float* dout, int ring, int steps, bool io16) {
   HIP_TRY(b->sync.ensure(b->S, b->stream));
   const size_t per = (size_t)b->S * b->block / (io16 ? 2 : 1);
@@ -843,14 +856,23 @@ static int flow_steps(AspNsBatch* b, const float* din, float* dout, int ring, in
     const int v = atoi(e);
     if (v >= 2 && v <= kHandoffMaxSteps) maxm = v;
   }
+  int walk = b->flow_walk != 0 ? b->flow_walk : kFlowWalkAuto;
+  if (b->flow_walk == 0)
+    if (const char* e = getenv("ASP_NS_FLOW_WALK")) {  // tuning: steps per workgroup of batches left on auto
+      const int v = atoi(e);
+      if (v >= 1 && v <= kHandoffMaxSteps) walk = v;  // (anything else is ignored, as the setter would refuse it)
+    }
   for (int k = 0; k < steps; k += maxm) {
     const int m = steps - k < maxm ? steps - k : maxm;
     if (b->kernel == 2)
       HIP_TRY(launch_ns_frame2_flow(io16, b->state, b->hist, b->tables, din, dout, b->S, b->stream, b->sync.seq,
                                     b->sync.abort, b->sync.count, m, k % ring, ring, per, b->flow_stamps));
-    else
+    else {
+      const int w = walk < m ? walk : m;
       HIP_TRY(launch_ns_frame1_flow(io16, b->state, b->hist, b->tables, din, dout, b->S, b->stream, b->sync.seq,
-                                    b->sync.abort, b->sync.count, m, k % ring, ring, per, b->flow_stamps));
+                                    b->sync.abort, b->sync.count, m, w, k % ring, ring, per, b->flow_stamps));
+      b->flow_chunks = (m + w - 1) / w;
+    }
     b->sync.enqueued(m);
   }
   return ASP_OK;
@@ -1369,6 +1391,19 @@ int AspNsBatch_LastEnqueueUs(AspNsBatch* b, double* us) {
 int AspNsBatch_SetFlow(AspNsBatch* b, int mode) {
   if (!b || mode < -1 || mode > 1) return fail(ASP_ERR_PARAM, "SetFlow: -1 (default), 0 (off) or 1 (on)");
   b->flow = mode;
+  return ASP_OK;
+}
+
+int AspNsBatch_SetFlowWalk(AspNsBatch* b, int steps) {
+  if (!b || steps < 0 || steps > kHandoffMaxSteps) return fail(ASP_ERR_PARAM, "SetFlowWalk: 0 (auto) or 1..64 steps per workgroup");
+  b->flow_walk = steps;
+  return ASP_OK;
+}
+
+// Diagnostic (tests only): the grid's y extent -- chunks of steps -- of the last pair-layout hand-off launch.
+int AspNsBatch_DebugFlowChunks(AspNsBatch* b, int* chunks) {
+  if (!b || !chunks) return fail(ASP_ERR_PARAM, "DebugFlowChunks: bad argument");
+  *chunks = b->flow_chunks;
   return ASP_OK;
 }
 

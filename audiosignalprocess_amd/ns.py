@@ -71,6 +71,8 @@ def load_library():
         "AspNsBatch_SetStream": [vp, vp],
         "AspNsBatch_SetSplit": [vp, ip],
         "AspNsBatch_SetFlow": [vp, ip],
+        "AspNsBatch_SetFlowWalk": [vp, ip],
+        "AspNsBatch_DebugFlowChunks": [vp, C.POINTER(C.c_int)],
         "AspNsBatch_DebugFlowDesync": [vp],
         "AspNsBatch_SetKernel": [vp, ip],
         "AspNsBatch_Synchronize": [vp],
@@ -279,6 +281,10 @@ class NsBatch:
     def set_flow(self, mode):
         """Hand-off build of the multi-frame entry points: -1 default, 0 off, 1 on (include/asp_ns.h)."""
         _check(self.lib.AspNsBatch_SetFlow(self.h, mode), "AspNsBatch_SetFlow")
+
+    def set_flow_walk(self, steps):
+        """Hand-off build: frame steps of a launch one workgroup walks; 0 auto, 1..64 forced (include/asp_ns.h)."""
+        _check(self.lib.AspNsBatch_SetFlowWalk(self.h, steps), "AspNsBatch_SetFlowWalk")
 
     def set_split(self, parts):
         _check(self.lib.AspNsBatch_SetSplit(self.h, parts), "AspNsBatch_SetSplit")

@@ -197,6 +197,15 @@ int AspNsBatch_SetKernel(AspNsBatch* b, int kernel);
  * A wait that times out (workgroups are dispatched in grid order, so it cannot) makes the next synchronising
  * call fail with ASP_ERR_HIP. */
 int AspNsBatch_SetFlow(AspNsBatch* b, int mode);
+/* Hand-off build, pair-layout kernel: how many consecutive frame steps of a launch one workgroup walks for its four
+ * streams (tables, barrier and lane set-up once per walk; only the walk's first step waits for a counter).
+ * 0 = auto (4 steps: short walks measured fastest, the whole launch puts every wave of the chip in the same
+ * phase); 1..64 force a length (the environment variable ASP_NS_FLOW_WALK does the same for batches left on
+ * auto).  Same results bit for bit for every value. */
+int AspNsBatch_SetFlowWalk(AspNsBatch* b, int steps);
+/* Test hook: the grid's y extent (chunks of steps = ceil(steps / walk)) of the batch's last hand-off launch of the
+ * pair-layout kernel; 0 before the first one. */
+int AspNsBatch_DebugFlowChunks(AspNsBatch* b, int* chunks);
 /* Test hook: puts the host's hand-off step counter one ahead of the device's, so that the next multi-frame
  * call's waits time out (about 0.2 s), its steps are skipped and the call (or the next synchronising one)
  * returns ASP_ERR_HIP; the counters are back in step afterwards and the batch needs AspNsBatch_Init. */

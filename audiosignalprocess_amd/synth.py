@@ -205,3 +205,35 @@ def nsx_frames(num_streams, num_frames, n, num_bands=1, seed=0, stream0=0, level
         x = (nz * lev) // 32768 + np.where(on, (tri * amp) // 32768, 0) // (1 if b == 0 else 8 * b)
         out[:, b] = np.clip(x, -32768, 32767).astype(np.int16).reshape(num_streams, num_frames, n).transpose(1, 0, 2)
     return out
+
+
+def agc_frames(num_streams, num_frames, n, num_bands=1, seed=0, stream0=0, level=8000, shift=0, gaps=True):
+    """AGC input, int16 [num_frames][num_bands][num_streams][n].  Integer only, regenerable from its arguments.
+
+    Speech-like and amplitude-modulated, since a steady noise does not move the analog loop.  Frame f of
+    stream s is at position p = (f + shift + 37 s) mod 300 of a programme: p < 80 talk at `level`; p < 110 a
+    noise floor of amplitude 30; p < 190 talk at level / 16; p < 250 all zero; else talk at 6 x level, which
+    clips.  gaps=False: talk at `level` instead of the all-zero stretch (a long silence holds the analog loop's
+    upward steps back for eight seconds).  Talk: a triangle of period 53 + 6 (s mod 5) samples whose amplitude follows a syllable pattern
+    over the frames (0 .. 4 quarters of the level), plus noise at an eighth of it.  The far end of a run is
+    band 0 of another seed.  Higher bands: an eighth of band 0's talk plus their own noise.
+    """
+    L = n * num_frames
+    s = np.arange(stream0, stream0 + num_streams, dtype=np.int64)
+    out = np.zeros((num_frames, num_bands, num_streams, n), np.int16)
+    t = np.arange(L, dtype=np.int64)[None, :]
+    f = t // n
+    p = (f + shift + 37 * s[:, None]) % 300
+    period = (53 + 6 * (s % 5))[:, None]
+    tri = np.abs(2 * 65536 * (t % period) // period - 65536) - 32768
+    syll = ((f * 7 + 3 * s[:, None]) // 3) % 5
+    amp = np.where((p < 80) | ((p >= 190) & (p < 250) & (not gaps)), level, np.where((p >= 110) & (p < 190), level // 16, np.where(p >= 250, 6 * level, 0)))
+    amp = amp * syll // 4
+    for b in range(num_bands):
+        seeds = ((9091 + 104729 * (s + 1000003 * seed) + 7919 * b) & 0xFFFFFFFF).astype(np.uint32)
+        nz = (_lcg_u32(seeds, 0, L).astype(np.int64) >> 16) - 32768
+        talk = (tri * amp) // 32768 // (1 if b == 0 else 8) + (nz * (amp // 8)) // 32768
+        x = np.where((p >= 80) & (p < 110), (nz * 30) // 32768, talk)
+        x = np.where((p >= 190) & (p < 250) & gaps, 0, x)
+        out[:, b] = np.clip(x, -32768, 32767).astype(np.int16).reshape(num_streams, num_frames, n).transpose(1, 0, 2)
+    return out

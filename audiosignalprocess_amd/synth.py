@@ -237,3 +237,33 @@ def agc_frames(num_streams, num_frames, n, num_bands=1, seed=0, stream0=0, level
         x = np.where((p >= 190) & (p < 250) & gaps, 0, x)
         out[:, b] = np.clip(x, -32768, 32767).astype(np.int16).reshape(num_streams, num_frames, n).transpose(1, 0, 2)
     return out
+
+
+def ts_chunks(num_streams, num_chunks, rate, channels=1, seed=0, stream0=0, click_every=7, level=700):
+    """Transient-suppressor input in float-S16 units: (data float32 [F][S][C][L], reference float32 [F][S][L]),
+    L = rate / 100.  Integer-valued samples, LCG noise and rational arithmetic only (no libm).
+
+    Channel c of stream s: level * n + 4 * level * e(f) * (m(t) + m(t-1) + m(t-2) + m(t-3)) / 4 with n, m two
+    LCG noises and e(f) a syllable envelope (0, 1/2, 1, 1/2 over four chunks, off every other 16 chunks), plus
+    a click every click_every chunks: amplitude 2000 * (1 + (k mod 6)) for the k-th click, alternating sign,
+    halving over six samples, a quarter of the way into the chunk.  The reference channel holds the clicks
+    alone (all zero in a chunk without one)."""
+    L = rate // 100
+    T = L * num_chunks
+    s = np.arange(stream0, stream0 + num_streams, dtype=np.int64)
+    f = np.arange(T) // L
+    env = np.array([0.0, 0.5, 1.0, 0.5])[f % 4] * ((f // 16) % 2 == 0)
+    click = np.zeros(T)
+    for k, c in enumerate(range(click_every // 2, num_chunks, click_every)):
+        a = 2000.0 * (1 + k % 6) * (1 if k % 2 == 0 else -1)
+        for j in range(6):
+            click[c * L + L // 4 + j] = a / (1 << j) * (1 if j % 2 == 0 else -1)
+    data = np.empty((num_streams, channels, T))
+    for c in range(channels):
+        n = _lcg_uniform((777 + 31 * seed + 7919 * s + 104729 * c) & 0xFFFFFFFF, 0, T)
+        m = _lcg_uniform((4242 + 17 * seed + 6007 * s + 15485863 * c) & 0xFFFFFFFF, 0, T + 3)
+        lp = (m[:, 3:] + m[:, 2:-1] + m[:, 1:-2] + m[:, :-3]) / 4.0
+        data[:, c] = np.rint(level * n + 4.0 * level * env[None, :] * lp + click[None, :])
+    data = data.astype(np.float32).reshape(num_streams, channels, num_chunks, L)
+    ref = np.broadcast_to(click.astype(np.float32).reshape(1, num_chunks, L), (num_streams, num_chunks, L))
+    return np.ascontiguousarray(data.transpose(2, 0, 1, 3)), np.ascontiguousarray(ref.transpose(1, 0, 2))

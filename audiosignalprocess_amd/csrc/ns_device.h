@@ -242,6 +242,35 @@ __device__ __forceinline__ void fdiv3(const float (&n)[3], const float (&d)[3], 
   q[0] = a.x; q[1] = a.y;
   q[2] = fdiv(n[2], d[2]);
 }
+// One step of a quantile tracker (ns_core.c:232-260) in the branch-free form of the frame kernels: delta = FACTOR /
+// max(density, 1) (the quotient by 1 is exact), the step carries its sign -- lq += (+QUANTILE delta) / n or (-(1 -
+// QUANTILE) delta) / n (products, quotients and x + (-y) are sign-symmetric) -- and the density moves where the new
+// lq lies within WIDTH of the log magnitude.  cnt = n - 1, cnt1 = n, rcnt1 = 1 / n (rounded) as floats.
+// The packed form serves a lane's two owned bins of ONE tracker (cnt, cnt1, rcnt1 wave-uniform); the scalar form
+// serves bin 128 of the three trackers at once, tracker s on its own lane with its own cnt / cnt1 / rcnt1: the same
+// IEEE operations on the same operands in the same order as three wave-uniform passes.
+__device__ __forceinline__ void tracker_step2(f32x2& lq, f32x2& den, f32x2 lm, float cnt, float cnt1, float rcnt1) {
+  const f32x2 dm = {fmax_raw(den.x, 1.0f), fmax_raw(den.y, 1.0f)};
+  const float fac = NS_FACTOR * 1.f, qp = NS_QUANTILE, qm = -(1.f - NS_QUANTILE), wd = NS_WIDTH;
+  const f32x2 delta = fdiv2(f32x2{fac, fac}, dm);
+  const f32x2 coef = {lm.x > lq.x ? qp : qm, lm.y > lq.y ? qp : qm};
+  const f32x2 rd = {rcnt1, rcnt1}, nd1 = {-cnt1, -cnt1};
+  {
+    const f32x2 a = coef * delta, q0 = a * rd;
+    lq = lq + __builtin_elementwise_fma(__builtin_elementwise_fma(nd1, q0, a), rd, q0);
+  }
+  const f32x2 a = f32x2{cnt, cnt} * den + f32x2{1.f / (2.f * wd), 1.f / (2.f * wd)}, q0 = a * rd;
+  const f32x2 nd = __builtin_elementwise_fma(__builtin_elementwise_fma(nd1, q0, a), rd, q0);
+  den = f32x2{fabsf(lm.x - lq.x) < wd ? nd.x : den.x, fabsf(lm.y - lq.y) < wd ? nd.y : den.y};
+}
+__device__ __forceinline__ void tracker_step1(float& lq, float& den, float lm, float cnt, float cnt1, float rcnt1) {
+  const float fac = NS_FACTOR * 1.f, qp = NS_QUANTILE, qm = -(1.f - NS_QUANTILE), wd = NS_WIDTH;
+  const float delta = fdiv(fac, fmax_raw(den, 1.0f));
+  const float coef = lm > lq ? qp : qm;
+  lq = lq + div_by_uniform(coef * delta, cnt1, rcnt1);
+  const float nd = div_by_uniform(cnt * den + 1.f / (2.f * wd), cnt1, rcnt1);
+  den = fabsf(lm - lq) < wd ? nd : den;
+}
 // ---- the two-streams-per-wave kernel (ns_kernels2.hip): four owned bins + bin 128 per lane
 __device__ __forceinline__ void fdiv5(const float (&n)[5], const float (&d)[5], float (&q)[5]) {
   const f32x2 a = fdiv2(f32x2{n[0], n[1]}, f32x2{d[0], d[1]});

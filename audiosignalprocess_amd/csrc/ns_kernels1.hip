@@ -14,6 +14,9 @@
 //     state row; bin 128 is computed on every lane (wave-uniform) and committed with the scalars;
 //   * per-stream scalars are wave-uniform: read from the scalar row with v_readlane, every
 //     data-independent branch of the reference is a scalar branch, written back with v_writelane;
+//   * independent wave-uniform chains with one formula are evaluated ONCE, each on its own lane: bin 128 of the three
+//     quantile trackers on lanes 48..50 of the scalar row, the flatness feature's exp beside bin 128's exp(-logLrt) --
+//     each value through the operations of its wave-uniform pass (bit-identical), no LDS, no barrier;
 //   * the three radix-4 passes go through a 1 KB LDS tile per wave (each lane computes half a
 //     butterfly, no duplicated arithmetic), the radix-2 tail through v_permlane32_swap (element p
 //     on lane L, p + 64 on lane L ^ 32), the real split through one LDS gather;
@@ -357,9 +360,7 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
     LOADV(LQ[0], V_LQ0) LOADV(LQ[1], V_LQ1) LOADV(LQ[2], V_LQ2)
     LOADV(DEN[0], V_DEN0) LOADV(DEN[1], V_DEN1) LOADV(DEN[2], V_DEN2)
     LOADV(quant, V_QUANT)
-    LOADT(LQ[0], V_LQ0) LOADT(LQ[1], V_LQ1) LOADT(LQ[2], V_LQ2)
-    LOADT(DEN[0], V_DEN0) LOADT(DEN[1], V_DEN1) LOADT(DEN[2], V_DEN2)
-    LOADT(quant, V_QUANT)
+    LOADT(quant, V_QUANT)  // (the trackers' bin-128 members stay on their lanes of the scalar row: phase 4)
     NS_STAMP(1)
     // ---- forward FFT (ns_core.c:886-911)
     *reinterpret_cast<float4*>(&tile[2 * lane]) = make_float4(wx0, wx1, wx2, wx3);
@@ -445,29 +446,38 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
     // ---- NoiseEstimation (ns_core.c:217-285)
     if (updates < NS_END_STARTUP_LONG) updates++;
     bool quant_new = false;
+    // Bin 128 of the three trackers: three independent chains with one formula, evaluated ONCE with tracker s on
+    // lane 48 + s -- where its lquantile tail already sits in the scalar row; its density tail, three lanes up in
+    // the same DPP row, comes down by one row shift, and n - 1 / n / 1 / n are built per lane from the three
+    // counters.  Every value goes through the operations of its own wave-uniform pass; the other lanes compute
+    // on whatever the row holds and are dropped by the masked merge.
+    constexpr int kLqLane = S_TAIL0 + V_LQ0, kDenLane = S_TAIL0 + V_DEN0;
+    static_assert(V_LQ1 == V_LQ0 + 1 && V_LQ2 == V_LQ0 + 2 && V_DEN1 == V_DEN0 + 1 && V_DEN2 == V_DEN0 + 2 &&
+                  kDenLane == kLqLane + 3 && kLqLane / 16 == (kDenLane + 2) / 16,
+                  "the tracker tails: three + three consecutive lanes of one DPP row");
+    float lqT = sv, denT = dpp_move<0x103>(sv);  // row_shl:3: lane L reads lane L + 3
+    float rcnt1v;
+    {
+      const int cntb = lanes3_bits<kLqLane>(counter[0], counter[1], counter[2]);
+      const float cntv = (float)cntb, cnt1v = (float)(cntb + 1);
+      rcnt1v = fdiv(1.f, cnt1v);  // == 1.f / cnt1 (cnt1 = 1 .. 201)
+      tracker_step1(lqT, denT, lmagn[2], cntv, cnt1v, rcnt1v);
+    }
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
-      const float cnt = (float)counter[s];
-      const float cnt1 = (float)(counter[s] + 1);
-      const float rcnt1 = fdiv(1.f, cnt1);  // == 1.f / cnt1 (cnt1 = 1 .. 201)
       {
-        // ns_core.c:232-260 with two of its three branches folded into the arithmetic (same roundings):
-        // delta = FACTOR / max(density, 1) (the quotient by 1 is exact), and the step carries its sign,
-        // lq += (+QUANTILE delta) / n or (-(1 - QUANTILE) delta) / n (products, quotients and x + (-y)
-        // are sign-symmetric)
-        F3 den(DEN[s]), lq(LQ[s]);
-        const F3 lm(lmagn);
-        const F3 delta = fdiv3v(F3(NS_FACTOR * 1.f), max3(den, 1.0f));
-        const F3 coef = sel3(gt3(lm, lq), F3(NS_QUANTILE), F3(-(1.f - NS_QUANTILE)));
-        lq = lq + div_by_uniform3(coef * delta, cnt1, rcnt1);
-        const F3 nd = div_by_uniform3(cnt * den + 1.f / (2.f * NS_WIDTH), cnt1, rcnt1);
-        den = sel3(lt3(abs3(lm - lq), F3(NS_WIDTH)), nd, den);
-        den.store(DEN[s]);
-        lq.store(LQ[s]);
+        const float cnt = (float)counter[s];
+        const float cnt1 = (float)(counter[s] + 1);
+        const float rcnt1 = lane_bcast(rcnt1v, kLqLane + s);
+        f32x2 lq = {LQ[s][0], LQ[s][1]}, den = {DEN[s][0], DEN[s][1]};
+        tracker_step2(lq, den, f32x2{lmagn[0], lmagn[1]}, cnt, cnt1, rcnt1);
+        LQ[s][0] = lq.x; LQ[s][1] = lq.y;
+        DEN[s][0] = den.x; DEN[s][1] = den.y;
       }
       if (counter[s] >= NS_END_STARTUP_LONG) {
         counter[s] = 0;
         if (updates >= NS_END_STARTUP_LONG) {
+          LQ[s][2] = lane_bcast(lqT, kLqLane + s);  // the publish wants the tail wave-uniform
           exp_f32_via_f64_n<NS3>(LQ[s], quant, exp2s);
           quant_new = true;
         }
@@ -475,13 +485,18 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
       counter[s]++;
     }
     if (updates < NS_END_STARTUP_LONG) {
+      LQ[2][2] = lane_bcast(lqT, kLqLane + 2);
       exp_f32_via_f64_n<NS3>(LQ[2], quant, exp2s);
       quant_new = true;
     }
 #pragma unroll
     for (int k = 0; k < NS3; ++k) noise[k] = quant[k];
-    STORE3(V_LQ0, LQ[0]) STORE3(V_LQ1, LQ[1]) STORE3(V_LQ2, LQ[2])
-    STORE3(V_DEN0, DEN[0]) STORE3(V_DEN1, DEN[1]) STORE3(V_DEN2, DEN[2])
+#pragma unroll
+    for (int s = 0; s < 3; ++s) sa.st2(kOffVec + (V_LQ0 + s) * kVecStride, 2 * lane, LQ[s][0], LQ[s][1]);
+#pragma unroll
+    for (int s = 0; s < 3; ++s) sa.st2(kOffVec + (V_DEN0 + s) * kVecStride, 2 * lane, DEN[s][0], DEN[s][1]);
+    sv = mergelanes_vgpr<(7ull << kLqLane)>(sv, lqT);
+    sv = mergelanes_vgpr<(7ull << kDenLane)>(sv, dpp_move<0x113>(denT));  // row_shr:3: lane L reads lane L - 3
     // the published quantile changes once in ~67 frames past start-up (a tracker publishes every 200
     // frames, ns_core.c:262-270): its row is written back only then (wave-uniform branch)
     if (quant_new) STORE3(V_QUANT, quant)
@@ -574,13 +589,16 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
     NS_STAMP(7)
     // ---- ComputeSpectralFlatness (ns_core.c:523-556)
     float fd0 = SC_F(S_FD0), fd4 = SC_F(S_FD4), fd6 = SC_F(S_FD6);
+    // (its exponential is evaluated beside bin 128's of exp(-logLrt), each on a lane of one call, once logLrt is
+    // updated: the feature is finished there, in front of its first readers, the histogram and the tanh)
+    float flatArg, flatDen;
     {
       float num = flatNum;
       float den = sumMagn - lane_bcast(magn[0], 0);
       den = DIV129(den);
       num = DIV129(num);
-      const float spectralTmp = fdiv(exp_f32_via_f64(num, exp2s), den);
-      fd0 += NS_SPECT_FL_TAVG * (spectralTmp - fd0);
+      flatArg = num;
+      flatDen = den;
     }
     // ---- ComputeSpectralDifference (ns_core.c:595-634)
     {
@@ -610,7 +628,45 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
     }
 
     NS_STAMP(8)
-    // ---- histograms / prior model (FeatureUpdate, ns_core.c:766-790)
+    // ---- SpeechNoiseProb (ns_core.c:642-749): the likelihood-ratio update
+    {
+      float t1[NS3], lt1[NS3];
+#pragma unroll
+      for (int k = 0; k < NS3; ++k) t1[k] = 1.f + 2.f * snrLocPrior[k];
+      log_f32_via_tab_n<NS3>(t1, lt1, logts);
+      float tn[NS3], td3[NS3], t2v[NS3];
+#pragma unroll
+      for (int k = 0; k < NS3; ++k) {
+        tn[k] = 2.f * snrLocPrior[k];
+        td3[k] = t1[k] + 0.0001f;
+      }
+      fdiv3(tn, td3, t2v);
+#pragma unroll
+      for (int k = 0; k < NS3; ++k) {
+        const float t2 = t2v[k];
+        const float besselTmp = (snrLocPost[k] + 1.f) * t2;
+        logLrt[k] += NS_LRT_TAVG * (besselTmp - lt1[k] - logLrt[k]);
+      }
+    }
+    float logLrtTimeAvgKsum = SUM3(logLrt);
+    logLrtTimeAvgKsum = DIV129(logLrtTimeAvgKsum);
+    // exp(-logLrt) of the lane's two bins, and two independent wave-uniform exponentials in the third slot of the
+    // same call: the flatness feature's on lane 0, bin 128's on every other lane (read back from lane 1)
+    float ev[NS3];
+    {
+      float nl[NS3];
+#pragma unroll
+      for (int k = 0; k < NS3; ++k) nl[k] = -logLrt[k];
+      nl[2] = lane == 0 ? flatArg : nl[2];
+      exp_f32_via_f64_n<NS3>(nl, ev, exp2s);
+      const float spectralTmp = fdiv(lane_bcast(ev[2], 0), flatDen);  // ns_core.c:551-555
+      fd0 += NS_SPECT_FL_TAVG * (spectralTmp - fd0);
+      ev[2] = lane_bcast(ev[2], 1);
+    }
+
+    NS_STAMP(9)
+    // ---- histograms / prior model (FeatureUpdate, ns_core.c:766-790): the new flatness and difference features, the
+    // previous frame's average LRT
     float fd3 = SC_F(S_FD3);  // previous frame's average LRT feeds the histogram
     PriorModel pm;
     pm.p0 = SC_F(S_PMP0);
@@ -650,30 +706,6 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
         }
       }
     }
-
-    NS_STAMP(9)
-    // ---- SpeechNoiseProb (ns_core.c:642-749)
-    {
-      float t1[NS3], lt1[NS3];
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) t1[k] = 1.f + 2.f * snrLocPrior[k];
-      log_f32_via_tab_n<NS3>(t1, lt1, logts);
-      float tn[NS3], td3[NS3], t2v[NS3];
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) {
-        tn[k] = 2.f * snrLocPrior[k];
-        td3[k] = t1[k] + 0.0001f;
-      }
-      fdiv3(tn, td3, t2v);
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) {
-        const float t2 = t2v[k];
-        const float besselTmp = (snrLocPost[k] + 1.f) * t2;
-        logLrt[k] += NS_LRT_TAVG * (besselTmp - lt1[k] - logLrt[k]);
-      }
-    }
-    float logLrtTimeAvgKsum = SUM3(logLrt);
-    logLrtTimeAvgKsum = DIV129(logLrtTimeAvgKsum);
     fd3 = logLrtTimeAvgKsum;
     {
       const float widthPrior0 = NS_WIDTH_PR_MAP, widthPrior1 = 2.f * NS_WIDTH_PR_MAP,
@@ -703,10 +735,6 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
     float probSpeech[NS3];
     {
       const float gainPrior = fdiv(1.f - priorSpeechProb, priorSpeechProb + 0.0001f);
-      float nl[NS3], ev[NS3];
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) nl[k] = -logLrt[k];
-      exp_f32_via_f64_n<NS3>(nl, ev, exp2s);
       {
         float pd[NS3];
         const float ones[NS3] = {1.f, 1.f, 1.f};

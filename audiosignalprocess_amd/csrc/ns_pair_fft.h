@@ -217,6 +217,18 @@ __device__ __forceinline__ float setlane_vgpr(float row, float val) {
   asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(row) : "v"(val), "s"(mask));
   return row;
 }
-
+// The masked lane merge: the lanes of MASK take their own lane's `val`, the others keep `row`.  For values that are
+// NOT wave-uniform: independent chains evaluated side by side, one per lane, go back into the scalar row at once.
+template <unsigned long long MASK>
+__device__ __forceinline__ float mergelanes_vgpr(float row, float val) {
+  const unsigned long long mask = MASK;
+  asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(row) : "v"(val), "s"(mask));
+  return row;
+}
+// Three wave-uniform words as a per-lane vector: lane K holds a, lane K + 1 b, every other lane c (so lane K + 2 too).
+template <int K>
+__device__ __forceinline__ int lanes3_bits(int a, int b, int c) {
+  return __float_as_int(writelane_bits<K + 1>(writelane_bits<K>(__int_as_float(c), a), b));
+}
 
 }  // namespace aspns_pair

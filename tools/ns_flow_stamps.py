@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from audiosignalprocess_amd.ns import NsBatch
 from audiosignalprocess_amd.synth import ns_frames
-names = ["in+energy", "fftF", "g2loads+magn+log", "sums1", "trackers", "startup", "snr", "flat+diff", "hist", "speechprob",
+names = ["in+energy", "fftF", "g2loads+magn+log", "sums1", "trackers", "startup", "snr", "flat+diff", "lrt+exp", "hist+prob",
          "noiseupd", "gain", "ifft", "gainfac", "ola", "scalars", "drain"]
 for S in [int(a) for a in sys.argv[1:]] or [4096, 8192]:
     g = NsBatch(S, policy=1)

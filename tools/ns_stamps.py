@@ -4,7 +4,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from audiosignalprocess_amd.ns import NsBatch
 from audiosignalprocess_amd.synth import ns_frames
-names = ["in+energy", "fftF", "g2loads+magn+log", "sums1", "trackers", "startup", "snr", "flat+diff", "hist", "speechprob", "noiseupd", "gain", "ifft", "gainfac", "ola", "scalars"]
+names = ["in+energy", "fftF", "g2loads+magn+log", "sums1", "trackers", "startup", "snr", "flat+diff", "lrt+exp", "hist+prob", "noiseupd", "gain", "ifft", "gainfac", "ola", "scalars"]
 for S in (8, 4096):
     g = NsBatch(S, policy=1)
     x = torch.from_numpy(ns_frames(S, 260, frame0=0)).cuda()

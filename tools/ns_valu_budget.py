@@ -7,8 +7,14 @@ no libm fallback) are asserted, so the code between two marks is what one wave e
 Prints, per phase, the instruction classes of the <IO16 = false> instantiation; branch targets that
 survive are listed so that a cold block cannot hide inside a phase.
 
-usage: tools/ns_valu_budget.py [source.hip] [--dump out.s] [extra hipcc flags...]
+--flow selects the hand-off instantiation <IO16 = false, FLOW = true> (the headline of bench.py) instead of the first
+<false, ...> match (the plain build), compiles with the per-file flags of build.py (EXTRA["ns_kernels1.hip"]: the
+register figures of that instantiation depend on them) and adds a "loop body" row: what lies between the header of
+the step loop and its back edge, i.e. one steady-state frame step without the once-per-chunk set-up in front of it.
+
+usage: tools/ns_valu_budget.py [source.hip] [--flow] [--dump out.s] [extra hipcc flags...]
 """
+import importlib.util
 import collections
 import os
 import re
@@ -17,8 +23,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ["in+energy", "fftF", "g2loads+magn+log", "sums1", "trackers", "startup", "snr", "flat+diff", "hist",
-         "speechprob", "noiseupd", "gain", "ifft", "gainfac", "ola", "scalars", "tail"]
+NAMES = ["in+energy", "fftF", "g2loads+magn+log", "sums1", "trackers", "startup", "snr", "flat+diff", "lrt+exp",
+         "hist+prob", "noiseupd", "gain", "ifft", "gainfac", "ola", "scalars", "tail"]
 
 
 def classify(op):
@@ -75,26 +81,36 @@ def main():
     args = sys.argv[1:]
     src = os.path.join(ROOT, "audiosignalprocess_amd", "csrc", "ns_kernels1.hip")
     dump = None
+    flow = False
     extra = []
     i = 0
     while i < len(args):
         if args[i] == "--dump":
             dump = args[i + 1]
             i += 2
+        elif args[i] == "--flow":
+            flow = True
+            i += 1
         elif args[i].endswith(".hip"):
             src = args[i]
             i += 1
         else:
             extra.append(args[i])
             i += 1
+    perfile = ["-mllvm", "-amdgpu-kernarg-preload-count=8"]
+    if flow:  # the product's own flags for this file (a plain list in build.py; loaded without importing the package)
+        spec = importlib.util.spec_from_file_location("asp_build", os.path.join(ROOT, "audiosignalprocess_amd", "build.py"))
+        bld = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(bld)
+        perfile = list(bld.EXTRA["ns_kernels1.hip"])
     out = dump or os.path.join(tempfile.mkdtemp(), "k.s")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-mllvm",
-           "-amdgpu-kernarg-preload-count=8", "-DNS1_BUDGET", "-I" + os.path.join(ROOT, "include"),
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"] + perfile + ["-DNS1_BUDGET", "-I" + os.path.join(ROOT, "include"),
            "-I" + os.path.join(ROOT, "audiosignalprocess_amd", "csrc"), "-S", "--cuda-device-only", "-o", out, src] + extra
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     lines = open(out).read().split("\n")
-    # the <false> instantiation: from its label to its s_endpgm
-    start = next(i for i, l in enumerate(lines) if re.match(r"^_Z.*kernelILb0E.*:", l))
+    # the <false, ...> instantiation (--flow: <false, true>): from its label to its s_endpgm
+    want = r"^_Z.*kernelILb0ELb1E.*:" if flow else r"^_Z.*kernelILb0E.*:"
+    start = next(i for i, l in enumerate(lines) if re.match(want, l))
     body = []
     for l in lines[start + 1:]:
         body.append(l)
@@ -103,7 +119,23 @@ def main():
     phase = -1
     per = collections.OrderedDict()
     labels = collections.defaultdict(list)
-    for l in body:
+    # the step loop (--flow): the backward branch with the longest reach that spans phase marks, and its target
+    loop = None
+    if flow:
+        where = {}
+        for n, l in enumerate(body):
+            m = re.match(r"^(\.LBB\S+):", l.strip())
+            if m:
+                where[m.group(1)] = n
+        marks = [n for n, l in enumerate(body) if l.strip().startswith("; NS_PHASE")]
+        for n, l in enumerate(body):
+            t = l.split()
+            if len(t) >= 2 and t[0].startswith(("s_cbranch", "s_branch")) and where.get(t[1], n) < n:
+                h = where[t[1]]
+                if any(h < k < n for k in marks) and (loop is None or n - h > loop[1] - loop[0]):
+                    loop = (h, n)
+    inloop = collections.Counter()
+    for n, l in enumerate(body):
         t = l.strip()
         m = re.match(r"; NS_PHASE (\d+)", t)
         if m:
@@ -116,6 +148,8 @@ def main():
             continue
         op = t.split()[0]
         per.setdefault(phase, collections.Counter())[classify(op)] += 1
+        if loop and loop[0] <= n <= loop[1]:
+            inloop[classify(op)] += 1
     cols = list(VALU) + ["s_nop", "salu", "lds", "vmem", "waitcnt", "branch"]
     print("%-18s %5s %6s | " % ("phase", "VALU", "cycles") + " ".join("%7s" % c for c in cols))
     tot = collections.Counter()
@@ -127,6 +161,13 @@ def main():
         tot.update(c)
     v = sum(tot[k] for k in VALU)
     print("%-18s %5d %6.0f | " % ("total", v, sum(tot[k] * PRICE[k] for k in VALU)) + " ".join("%7d" % tot[k] for k in cols))
+    if flow:
+        if loop:
+            v = sum(inloop[k] for k in VALU)
+            print("%-18s %5d %6.0f | " % ("loop body", v, sum(inloop[k] * PRICE[k] for k in VALU)) + " ".join("%7d" % inloop[k] for k in cols)
+                  + "   (%s .. its back edge)" % body[loop[0]].strip().rstrip(":"))
+        else:
+            print("loop body: no backward branch across the phase marks found")
     m = re.search(r"\.vgpr_count:\s+(\d+)", "\n".join(lines[::-1]))
     for l in lines:
         if "vgpr_count" in l or "sgpr_count" in l or "vgpr_spill" in l:

@@ -11,15 +11,20 @@
 //
 // The chunked form (ns_kernels1.hip, NsFlowArgs::walk): blockIdx.y is a CHUNK of C consecutive steps, and workgroup
 // (x, c) walks steps c C .. min(steps, (c + 1) C) - 1 of its streams in a loop.  Only the chunk's first step waits
-// (for the wave of chunk c - 1, dispatched earlier: the same argument as above); between two steps of its own the
-// wave drains its stores -- which is also what lets it read them back -- publishes seq[s], and goes on.  seq[s] still
-// counts the steps stream s has completed, after every step.  With C = steps no workgroup waits for another one of
-// the launch (only for the previous launch, which stream order has finished): nothing then rests on dispatch order.
-// C = 1 is the form above.  The host picks C (ns_api.hip, flow_walk).
+// (for the wave of chunk c - 1, dispatched earlier: the same argument as above).  Nobody else may touch the stream's
+// state before the walk ends, so between two steps of its own the wave neither drains nor publishes: it keeps the
+// hot part of the state on the chip (an LDS image, copied in behind the wait), and after the walk's last step writes
+// it back, drains, and publishes seq[s] ONCE, as the step count at the walk's end.  seq[s] counts the steps stream s
+// has completed AND handed back to memory: it advances once per walk (by C, or by what is left of the launch), state
+// in memory is consistent at every value seq[s] takes, and the only value the host may rely on is the one after a
+// launch (handoff_host.h).  What stays in memory inside a walk and is read back there (rare paths) waits for the
+// wave's own outstanding stores first.  With C = steps no workgroup waits for another one of the launch (only for the
+// previous launch, which stream order has finished): nothing then rests on dispatch order.  C = 1 is the form above
+// with a copy in and a copy out around every step.  The host picks C (ns_api.hip, flow_walk).
 //
 // What orders the two is a per-stream step counter in memory, seq[s]:
-//   * the wave that has finished step k of stream s drains every store it issued (handoff_drain:
-//     s_waitcnt vmcnt(0)), then one lane stores seq[s] = k + 1 (handoff_publish);
+//   * the wave that has finished step k of stream s (chunked form: the last step k of its walk) drains every store it
+//     issued (handoff_drain: s_waitcnt vmcnt(0)), then one lane stores seq[s] = k + 1 (handoff_publish);
 //   * the wave of step k + 1 polls seq[s] (handoff_wait) before its first access to what is handed off.
 // Every access to what a stream's steps hand each other is an sc1 access: write-through stores, loads that
 // bypass the CU's L1 (the buffer intrinsics with kSc1, or agent-scope relaxed atomics).  This is the form

@@ -17,7 +17,8 @@ inline bool handoff_env_default(const char* var) {
 }
 
 struct HandoffSync {
-  unsigned* seq = nullptr;    // [S] completed hand-off steps per stream (== count between calls)
+  unsigned* seq = nullptr;    // [S] completed hand-off steps per stream (== count between calls; inside a launch a
+                              // kernel may advance it by several steps at once: only the value after a launch counts)
   unsigned* abort = nullptr;  // 16 B: word 0 != 0 after a wait timed out
   unsigned count = 0;         // hand-off steps enqueued so far
   bool unchecked = false;     // hand-off launches enqueued since the abort word was last read

@@ -842,7 +842,9 @@ static bool flow_applies(const AspNsBatch* b, int steps) {
 // every wave of the chip is in the same phase again, as with one launch per step.  8192 and 6000 streams (a ragged
 // last round) gain the same way.  AspNsBatch_SetFlowWalk / ASP_NS_FLOW_WALK force a length.
 // Why 4 and not 2 (level at 4096 streams, inside the run-to-run spread): 4 pays the set-up half as often and was not
-// behind at any batch size or ring measured.
+// behind at any batch size or ring measured.  A walk also bounds the state traffic: the hot part of a stream's block
+// is copied into LDS once per walk and written back once (ns_kernels1.hip, "the resident state block"), so C steps
+// move it once instead of C times, and seq[s] advances once per walk; C = 1 copies in and out around every step.
 constexpr int kFlowWalkAuto = 4;
 
 // K steps of the hand-off build on the batch's stream: launches of up to kHandoffMaxSteps consecutive frame

@@ -59,20 +59,30 @@ __device__ __forceinline__ const P* ns_cold(const P* p) {  // (a wave-uniform po
 }
 
 // ---- the hand-off build (FLOW): consecutive frame steps overlap on the chip (the protocol: handoff.h).
-// What a stream's steps hand each other is its state block: every state access of this build is sc1; `in` /
-// `out` frames and the constant tables stay plain (non-temporal frame accesses were measured and dropped: level with a
+// What a stream's walks hand each other is its state block: every state access of this build that reaches memory is
+// sc1; `in` / `out` frames and the constant tables stay plain (non-temporal frame accesses were measured and dropped: level with a
 // ring of 100 frames, 0.9 us slower per step with a ring of 20, which they keep out of the Infinity Cache:
 // profiles/r05_ns_walk_ab.txt).  Step j of a launch reads / writes ring slot (slot0 + j) % ring.
 //
 // The launch is cut into chunks of `walk` consecutive steps: workgroup (x, c) WALKS steps c walk .. min(steps, (c + 1)
 // walk) - 1 of its four streams, one after the other.  What does not change from step to step -- the tables in LDS and
 // the one barrier behind them, the lane constants, the stream's buffer descriptor -- is set up once per chunk, and only
-// the chunk's first step waits for a counter (the wave's own previous step needs no poll: it drains its stores, publishes,
-// and goes on).  walk == 1 is one step per workgroup; walk == steps leaves no dependency between workgroups at all --
-// and every wave of the chip in the same phase again: short walks measured fastest (ns_api.hip, flow_walk).
+// the chunk's first step waits for a counter.  walk == 1 is one step per workgroup; walk == steps leaves no dependency
+// between workgroups at all -- and every wave of the chip in the same phase again: short walks measured fastest
+// (ns_api.hip, flow_walk).
+//
+// The resident state block: nobody else may touch a stream's state before its walk ends, so the hot part of the block
+// -- its first kImgDwords dwords in ns_layout.h order: scalars and row tails, both sliding-buffer carries, rows V_LQ0 ..
+// V_AVGPAUSE -- lives in an LDS image of the wave for the length of the walk.  The wave copies it in once behind the
+// chunk's wait, every step goes through the image (StateAcc), and after the walk's last step the wave writes the image
+// back (sc1), drains and publishes seq[stream] = want + (the walk's end): once per walk.  Between two of its own steps
+// a wave neither drains nor publishes; the scalar row stays in its register.  What stays in memory inside a walk -- the
+// start-up rows V_INITMAGN / V_PARAMNOISE and the histograms -- is read back only in rare paths, which wait for the
+// wave's outstanding stores themselves.  Each wave touches only its own image: no barrier is added.
 struct NsFlowArgs {
   HandoffArgs hand;
-  unsigned want;      // step 0 of the launch is step `want` of every stream
+  unsigned want;      // step 0 of the launch is step `want` of every stream (seq[s] == want on entry; a walk over
+                      // steps j .. e - 1 of the launch leaves seq[s] == want + e, with no value in between)
   int slot0;          // ring slot of that step; step j of the launch uses slot (slot0 + j) % ring
   int ring;
   unsigned per;       // floats between two ring slots of `in` / `out`
@@ -91,37 +101,86 @@ __device__ __forceinline__ float4 load_frame4(const float* in, size_t idx) {
   }
 }
 
-// One stream's state block: `uni` is a wave-uniform dword offset, `vec` the lane's dword offset.
+// the hand-off build's resident part of a stream block (dwords): everything in front of the cold rows
+constexpr int kImgDwords = aspns::kOffVec + aspns::V_HOT_COUNT * aspns::kVecStride;
+constexpr int kImgVec4 = kImgDwords / (64 * 4);  // 16-byte pieces per lane of a whole-image copy
+static_assert(kImgDwords == 1792 && kImgDwords % (64 * 4) == 0, "the image is copied as whole 16-byte pieces per lane");
+typedef __attribute__((address_space(3))) float lds_f32;
+typedef __attribute__((address_space(3))) f32x2v lds_f32x2;
+typedef __attribute__((address_space(3))) f32x4v lds_f32x4;
+
+// One stream's state block: `uni` is a wave-uniform dword offset (a constant at every call site), `vec` the lane's
+// dword offset.  Hand-off build: offsets inside the resident part address the wave's LDS image, the others memory (sc1).
 template <bool FLOW>
 struct StateAcc {
   float* st;
   __amdgpu_buffer_rsrc_t rs;
-  __device__ __forceinline__ explicit StateAcc(float* p) : st(p) {
+  lds_f32* img;
+  __device__ __forceinline__ StateAcc(float* p, float* image) : st(p), img((lds_f32*)image) {
     if constexpr (FLOW) rs = __builtin_amdgcn_make_buffer_rsrc(p, 0, aspns::kStreamDwords * 4, 0x00020000);
   }
   __device__ __forceinline__ float ld1(int uni, int vec) const {
-    if constexpr (FLOW) return sc1_load1(rs, vec * 4, uni * 4);
+    if constexpr (FLOW) return uni < kImgDwords ? img[uni + vec] : sc1_load1(rs, vec * 4, uni * 4);
     else return st[uni + vec];
   }
   __device__ __forceinline__ float2 ld2(int uni, int vec) const {
-    if constexpr (FLOW) return sc1_load2(rs, vec * 4, uni * 4);
-    else return *reinterpret_cast<const float2*>(st + uni + vec);
+    if constexpr (FLOW) {
+      if (uni >= kImgDwords) return sc1_load2(rs, vec * 4, uni * 4);
+      const f32x2v v = *reinterpret_cast<const lds_f32x2*>(img + uni + vec);
+      return make_float2(v.x, v.y);
+    } else {
+      return *reinterpret_cast<const float2*>(st + uni + vec);
+    }
   }
   __device__ __forceinline__ float4 ld4(int uni, int vec) const {
-    if constexpr (FLOW) return sc1_load4(rs, vec * 4, uni * 4);
-    else return *reinterpret_cast<const float4*>(st + uni + vec);
+    if constexpr (FLOW) {
+      if (uni >= kImgDwords) return sc1_load4(rs, vec * 4, uni * 4);
+      const f32x4v v = *reinterpret_cast<const lds_f32x4*>(img + uni + vec);
+      return make_float4(v.x, v.y, v.z, v.w);
+    } else {
+      return *reinterpret_cast<const float4*>(st + uni + vec);
+    }
   }
   __device__ __forceinline__ void st1(int uni, int vec, float v) const {
-    if constexpr (FLOW) sc1_store1(rs, vec * 4, uni * 4, v);
-    else st[uni + vec] = v;
+    if constexpr (FLOW) {
+      if (uni < kImgDwords) img[uni + vec] = v;
+      else sc1_store1(rs, vec * 4, uni * 4, v);
+    } else {
+      st[uni + vec] = v;
+    }
   }
   __device__ __forceinline__ void st2(int uni, int vec, float a, float b) const {
-    if constexpr (FLOW) sc1_store2(rs, vec * 4, uni * 4, a, b);
-    else *reinterpret_cast<float2*>(st + uni + vec) = make_float2(a, b);
+    if constexpr (FLOW) {
+      if (uni < kImgDwords) *reinterpret_cast<lds_f32x2*>(img + uni + vec) = f32x2v{a, b};
+      else sc1_store2(rs, vec * 4, uni * 4, a, b);
+    } else {
+      *reinterpret_cast<float2*>(st + uni + vec) = make_float2(a, b);
+    }
   }
   __device__ __forceinline__ void st4(int uni, int vec, float4 x) const {
-    if constexpr (FLOW) sc1_store4(rs, vec * 4, uni * 4, x);
-    else *reinterpret_cast<float4*>(st + uni + vec) = x;
+    if constexpr (FLOW) {
+      if (uni < kImgDwords) *reinterpret_cast<lds_f32x4*>(img + uni + vec) = f32x4v{x.x, x.y, x.z, x.w};
+      else sc1_store4(rs, vec * 4, uni * 4, x);
+    } else {
+      *reinterpret_cast<float4*>(st + uni + vec) = x;
+    }
+  }
+  // the whole image: memory -> LDS (`v` are the loads of image_request, issued earlier), LDS -> memory
+  __device__ __forceinline__ void image_request(int lane, float4 (&v)[kImgVec4]) const {
+#pragma unroll
+    for (int i = 0; i < kImgVec4; ++i) v[i] = sc1_load4(rs, lane * 16, i * 1024);
+  }
+  __device__ __forceinline__ void image_fill(int lane, const float4 (&v)[kImgVec4]) const {
+#pragma unroll
+    for (int i = 0; i < kImgVec4; ++i)
+      *reinterpret_cast<lds_f32x4*>(img + i * 256 + 4 * lane) = f32x4v{v[i].x, v[i].y, v[i].z, v[i].w};
+  }
+  __device__ __forceinline__ void image_write_back(int lane) const {
+#pragma unroll
+    for (int i = 0; i < kImgVec4; ++i) {
+      const f32x4v v = *reinterpret_cast<const lds_f32x4*>(img + i * 256 + 4 * lane);
+      sc1_store4(rs, lane * 16, i * 1024, make_float4(v.x, v.y, v.z, v.w));
+    }
   }
 };
 
@@ -146,7 +205,7 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
 #else
   // diagnostic stamps (never passed by the product entry points).  stamp_mode 0: the 16 phase stamps
   // (shader clock) of workgroup 0's first wave (hand-off build: of the middle of the launch, x = grid / 2,
-  // step = steps / 2, plus a 17th once that step's stores have drained).  stamp_mode 1 ("timeline"): every workgroup's first
+  // step = steps / 2, plus a 17th at that step's end: once its stores have drained where it is its walk's last).  stamp_mode 1 ("timeline"): every workgroup's first
   // wave records the 100 MHz real-time counter at its start, after its first loads, before its last
   // stores and at its end (4 values per workgroup) -- the launch-level picture.
   // (one wave-uniform word decides: the stamps cost the step loop of the hand-off build one scalar register)
@@ -182,6 +241,8 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
   __shared__ __align__(16) float wins[kAnal];
   __shared__ __align__(16) double exp2s[64];     // 2^(j/64) of the lean exp / tanh
   __shared__ __align__(16) double2 logts[128];   // {1/c, log c} of the table-driven log
+  // hand-off build: each wave's image of its stream's resident state block (the plain build has no use: no allocation)
+  __shared__ __align__(16) float imgs[FLOW ? 4 : 1][FLOW ? kImgDwords : 4];
   const int tid = threadIdx.x;
   // ---- prologue: every load of the first phase is issued before the first wait (table pieces
   // first: loads return in order, the LDS staging waits for them only)
@@ -204,7 +265,7 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
   const int stream = wave_live ? stream_raw : num_streams - 1;  // clamped for the loads
   float* __restrict__ st = state + (size_t)stream * kStreamDwords;
   int32_t* __restrict__ hist = hist_all + (size_t)stream * kHistDwords;
-  const StateAcc<FLOW> sa(st);
+  const StateAcc<FLOW> sa(st, FLOW ? imgs[wv] : nullptr);
   float* outj = out;  // this step's frame of `out` (hand-off build: its ring slot)
 
   // ---- scalars: lane k holds scalar k (wave-uniform values, read with v_readlane)
@@ -231,12 +292,12 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
                              : in + (size_t)slot * fa.per + frame_uni;
     s4in = load_frame4<IO16>(base, frame_lane);
   };
-  // hand-off build: the first state loads of step flow_j
+  // hand-off build: the first state reads of step flow_j, from the image (the scalar row is read once per walk and
+  // stays in `sv` between the walk's steps)
   auto flow_head = [&]() __attribute__((always_inline)) {
     NS_STAMP(0)
     outj = out + (size_t)flow_slot * fa.per;
     const int lane_c = ns_cold(lane);
-    sv = sa.ld1(kOffScalars, lane_c);
     const float4 ha = sa.ld4(kOffAnaHist, 4 * (lane_c < 24 ? lane_c : 23));
     const bool hsel = lane_c < 24;
     s4.x = hsel ? ha.x : s4in.x;
@@ -247,10 +308,11 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
     carryA = sa.ld2(kOffSynt, q2_c + 32 * (lane_c & 1));
     carryB = sa.ld2(kOffSynt, q2_c + 64);
   };
+  [[maybe_unused]] float4 img_v[FLOW ? kImgVec4 : 1];
   if constexpr (FLOW) {
     flow_load_in(flow_slot);
     if (wave_live) wave_live = handoff_wait(fa.hand, fa.want + flow_j, stream, lane);
-    flow_head();
+    if (wave_live) sa.image_request(lane, img_v);  // the copy-in: in flight behind the table staging
   } else {
     sv = st[kOffScalars + lane];
     float* hbuf = st + kOffAnaHist;
@@ -277,8 +339,15 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
   if (tid < 64) exp2s[tid] = exp2_v;
   if (tid < 128) logts[tid] = logt_v;
   if (tid >= 192) reinterpret_cast<float4*>(wins)[tid - 192] = win_v;
+  if constexpr (FLOW) {
+    if (wave_live) sa.image_fill(lane, img_v);
+  }
   __syncthreads();
   if (!wave_live) return;
+  if constexpr (FLOW) {
+    sv = sa.ld1(kOffScalars, lane);
+    flow_head();
+  }
   const float* tws = tabs;
   const float* spls = tabs + 3 * 64 * 4;
   const PairFftLane fl = pair_fft_lane(lane, diagbits);
@@ -301,14 +370,26 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
     flow_slot = flow_slot + 1u == (unsigned)fa.ring ? 0u : flow_slot + 1u;                     \
     if (flow_j + 1u < flow_end) flow_load_in(flow_slot);                                       \
   }
-  // the step is done for this stream: the hand-off build publishes it, every store of this wave drained first
-  // (the drain is also what lets the wave read its own stores back), and goes on to the chunk's next step
+  // the step is done for this stream.  Hand-off build: after the walk's last step the wave writes its image back,
+  // drains every store it has issued and publishes the walk; otherwise it goes on to its next step on the image (the
+  // wave-level fence orders this step's image writes, other lanes' too, in front of the next step's reads)
 #define NS_STREAM_DONE()                                                                       \
   if constexpr (FLOW) {                                                                        \
-    handoff_drain();                                                                           \
+    const bool walk_done_ = flow_j + 1u >= flow_end;                                           \
+    if (walk_done_) {                                                                          \
+      const int lane_w_ = ns_cold(lane);                                                       \
+      sa.st1(kOffScalars, lane_w_, sv);                                                        \
+      lds_sync1();                                                                             \
+      sa.image_write_back(lane_w_);                                                            \
+      handoff_drain();                                                                         \
+    }                                                                                          \
     NS_STAMP(16)                                                                               \
-    if (lane == 0) handoff_publish(fa.hand.seq + stream, fa.want + flow_j);                    \
-    if (++flow_j >= flow_end) return;                                                          \
+    if (walk_done_) {                                                                          \
+      if (lane == 0) handoff_publish(fa.hand.seq + stream, fa.want + flow_j);                  \
+      return;                                                                                  \
+    }                                                                                          \
+    ++flow_j;                                                                                  \
+    lds_sync1();                                                                               \
     flow_head();                                                                               \
     continue;                                                                                  \
   } else {                                                                                     \
@@ -556,7 +637,12 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
         noise[k] += (t2 / (float)(blockInd + 1));
         noise[k] /= NS_END_STARTUP_SHORT;
       }
-      STORE3(V_PARAMNOISE, pn)
+      if constexpr (FLOW) {  // (a cold row: in memory, the lane's offset from the opaque copy)
+        sa.st2(kOffVec + V_PARAMNOISE * kVecStride, 2 * ns_cold(lane), pn[0], pn[1]);
+        SC_SET_F(S_TAIL0 + V_PARAMNOISE, pn[2]);
+      } else {
+        STORE3(V_PARAMNOISE, pn)
+      }
     }
     if (blockInd < NS_END_STARTUP_LONG) {  // ns_core.c:1165-1169
       fd5 *= blockInd;
@@ -694,7 +780,11 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
           atomicAdd(&hist[lane_c * kHistStride + (int)div_by_uniform(fv, bw, rbw)], 1);  // agent scope (sc1)
       }
       if (mup3 == 0) {
+        // hand-off build: the no-return increments of the walk's earlier steps are complete before the window is
+        // read, and its clearing stores before the next step's increment
+        if constexpr (FLOW) handoff_drain();
         pm = close_histogram_window<FLOW>(hist, lane, mup1, mup0 >= 1, pm);
+        if constexpr (FLOW) handoff_drain();
         window_closed = true;
         mup3 = mup1;
         if (updateParsFlag == 1) {
@@ -789,11 +879,27 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
     // ---- Process: decision-directed Wiener gain (ns_core.c:985-1007, 1276-1307)
     float initMagn[NS3], pnoise[NS3];
     if (startup) {  // ns_core.c:1268-1272
-      LOAD3(initMagn, V_INITMAGN)
-      LOAD3(pnoise, V_PARAMNOISE)
+      if constexpr (FLOW) {
+        // the two cold rows stay in memory and are written and read back inside a walk: the wave's stores to them
+        // (this step's V_PARAMNOISE, the previous step's V_INITMAGN) are complete before it reads
+        handoff_drain();
+        const int lane2_c = 2 * ns_cold(lane);
+        const float2 im_ = sa.ld2(kOffVec + V_INITMAGN * kVecStride, lane2_c);
+        const float2 pn_ = sa.ld2(kOffVec + V_PARAMNOISE * kVecStride, lane2_c);
+        initMagn[0] = im_.x; initMagn[1] = im_.y;
+        pnoise[0] = pn_.x; pnoise[1] = pn_.y;
+        LOADT(initMagn, V_INITMAGN) LOADT(pnoise, V_PARAMNOISE)
 #pragma unroll
-      for (int k = 0; k < NS3; ++k) initMagn[k] += magn[k];
-      STORE3(V_INITMAGN, initMagn)
+        for (int k = 0; k < NS3; ++k) initMagn[k] += magn[k];
+        sa.st2(kOffVec + V_INITMAGN * kVecStride, lane2_c, initMagn[0], initMagn[1]);
+        SC_SET_F(S_TAIL0 + V_INITMAGN, initMagn[2]);
+      } else {
+        LOAD3(initMagn, V_INITMAGN)
+        LOAD3(pnoise, V_PARAMNOISE)
+#pragma unroll
+        for (int k = 0; k < NS3; ++k) initMagn[k] += magn[k];
+        STORE3(V_INITMAGN, initMagn)
+      }
     }
     float gainv[NS3];
     float gq1[NS3], gq2[NS3], snrP[NS3];
@@ -933,7 +1039,7 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
     SC_SET_F(S_FD6, fd6);
     SC_SET_I(S_BLOCKIND, blockInd);
     SC_SET_F(S_PRIORSPEECHPROB, priorSpeechProb);
-    sa.st1(kOffScalars, lane, sv);
+    if constexpr (!FLOW) sa.st1(kOffScalars, lane, sv);  // (hand-off build: with the image, at the walk's end)
     NS_STAMP(15)
     NS_STREAM_DONE()
   }
@@ -970,8 +1076,9 @@ hipError_t launch_ns_frame1(bool io16, float* state, int32_t* hist, const NsTabl
 }
 
 // `steps` consecutive frame steps of the hand-off build in one launch: steps want .. want + steps - 1 of every
-// stream (seq[s] == want on entry, want + steps on exit); step j reads / writes ring slot (slot0 + j) % ring of
-// in / out (slots `per` floats apart); a workgroup walks `walk` consecutive steps (NsFlowArgs).
+// stream (seq[s] == want on entry, want + steps on exit, advanced once per walk in between); step j reads / writes
+// ring slot (slot0 + j) % ring of in / out (slots `per` floats apart); a workgroup walks `walk` consecutive steps
+// (NsFlowArgs).
 hipError_t launch_ns_frame1_flow(bool io16, float* state, int32_t* hist, const NsTables* T,
                                  const float* in, float* out, int num_streams, hipStream_t s,
                                  unsigned* seq, unsigned* abort_w, unsigned want, int steps, int walk, int slot0,

@@ -267,3 +267,45 @@ def ts_chunks(num_streams, num_chunks, rate, channels=1, seed=0, stream0=0, clic
     data = data.astype(np.float32).reshape(num_streams, channels, num_chunks, L)
     ref = np.broadcast_to(click.astype(np.float32).reshape(1, num_chunks, L), (num_streams, num_chunks, L))
     return np.ascontiguousarray(data.transpose(2, 0, 1, 3)), np.ascontiguousarray(ref.transpose(1, 0, 2))
+
+
+def bf_chunks(num_streams, num_chunks, num_mics, seed=0, stream0=0, delay=2, level=3000, diffuse=60,
+              broadside=((0, 20), (70, 80)), offaxis=((24, 70),), silent=((20, 24),)):
+    """Microphone-array input for the beamformer in float-S16 units at the 16 kHz band rate: (input float32
+    [F][S][M][160], high band float32 [F][S][M][160]).  Integer-valued samples, LCG noise only (no libm).
+
+    Microphone c of stream s: a broadside source (the same low-passed noise on every microphone) during the chunk
+    ranges `broadside`, an off-axis source (another low-passed noise, delayed by c * delay samples) during
+    `offaxis`, and diffuse noise (independent per microphone, amplitude `diffuse`) everywhere except the ranges
+    `silent`, where every microphone is exactly zero.  The high band is the sources' sum at a quarter of the level
+    with its own per-microphone noise, silent in the same ranges."""
+    L = 160
+    T = L * num_chunks
+    s = np.arange(stream0, stream0 + num_streams, dtype=np.int64)
+    f = np.arange(T) // L
+
+    def gate(ranges):
+        g = np.zeros(T)
+        for a, b in ranges:
+            g[(f >= a) & (f < b)] = 1.0
+        return g
+
+    def lowpassed(salt, extra):
+        m = _lcg_uniform((salt + 97 * seed + 7919 * s) & 0xFFFFFFFF, 0, T + 3 + extra)
+        return (m[:, 3:] + m[:, 2:-1] + m[:, 1:-2] + m[:, :-3]) / 4.0
+
+    pad = delay * (num_mics - 1)
+    b = lowpassed(1357, 0) * gate(broadside)[None]
+    o = lowpassed(8642, pad)   # o[:, pad + t - c * delay] is the source at microphone c
+    live = 1.0 - gate(silent)
+    x = np.empty((num_streams, num_mics, T))
+    hi = np.empty((num_streams, num_mics, T))
+    for c in range(num_mics):
+        oc = o[:, pad - c * delay:pad - c * delay + T] * gate(offaxis)[None]
+        n = _lcg_uniform((2468 + 13 * seed + 6007 * s + 15485863 * c) & 0xFFFFFFFF, 0, T)
+        h = _lcg_uniform((9753 + 29 * seed + 104729 * s + 32452843 * c) & 0xFFFFFFFF, 0, T)
+        x[:, c] = np.rint((level * (b + oc) + diffuse * n) * live[None])
+        hi[:, c] = np.rint((0.25 * level * (b + oc) + diffuse * h) * live[None])
+    shape = (num_streams, num_mics, num_chunks, L)
+    return (np.ascontiguousarray(x.astype(np.float32).reshape(shape).transpose(2, 0, 1, 3)),
+            np.ascontiguousarray(hi.astype(np.float32).reshape(shape).transpose(2, 0, 1, 3)))

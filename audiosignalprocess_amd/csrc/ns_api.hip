@@ -590,8 +590,11 @@ struct AspNsBatch {
   // kHandoffMaxSteps consecutive frame steps of a K-step call per launch; a per-stream step counter in memory
   // orders step k + 1 of a stream behind its step k.  -1 = default (on for the pair-layout kernel), 0 = off, 1 = on.
   int flow = -1;
-  // Steps a workgroup of the pair-layout hand-off kernel walks (NsFlowArgs::walk): 0 = auto (kFlowWalkAuto), else forced.
+  // Steps a workgroup of the pair-layout hand-off kernel walks (NsFlowArgs::walk): 0 = auto (flow_walk_auto), else forced.
   int flow_walk = 0;
+  // Compute units of the batch's device: what the automatic walk is sized by; 0 = not asked yet (once per batch, at
+  // its first hand-off call).
+  int flow_cus = 0;
   int flow_chunks = 0;  // grid y of the last such launch (AspNsBatch_DebugFlowChunks)
   HandoffSync sync;
   // > 16 kHz: 1 or 2 high bands next to the low band (ns_core.c:1362-1414)
@@ -646,6 +649,13 @@ int AspNs_device_count(void) {
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess) return fail(ASP_ERR_NO_DEVICE, "hipGetDeviceCount", e);
   return n;
+}
+
+int AspNs_device_compute_units(int device, int* compute_units) {
+  if (!compute_units) return fail(ASP_ERR_PARAM, "AspNs_device_compute_units: bad argument");
+  hipError_t e = hipDeviceGetAttribute(compute_units, hipDeviceAttributeMultiprocessorCount, device);
+  if (e != hipSuccess) return fail(ASP_ERR_NO_DEVICE, "hipDeviceGetAttribute", e);
+  return ASP_OK;
 }
 
 int AspNsBatch_Create(AspNsBatch** out, int num_streams, int device) {
@@ -836,19 +846,30 @@ static bool flow_applies(const AspNsBatch* b, int steps) {
   return on && steps >= 2 && b->paired && b->kernel != 1 && b->fs != 8000 && b->timeline == nullptr;
 }
 
-// Steps per workgroup of a pair-layout hand-off launch of m steps.  Auto: kFlowWalkAuto.  Measured at 4096 streams
-// (profiles/r05_ns_walk_ab.txt): 2 and 4 steps 12.10-12.25 us per step, 8 and 16 steps 12.2-12.4 us, against
-// 12.4-12.5 us with one step per workgroup; the whole launch (64 steps, no workgroup waiting for another) 12.8 us --
-// every wave of the chip is in the same phase again, as with one launch per step.  8192 and 6000 streams (a ragged
-// last round) gain the same way.  AspNsBatch_SetFlowWalk / ASP_NS_FLOW_WALK force a length.
-// Why 4 and not 2 (level at 4096 streams, inside the run-to-run spread): 4 pays the set-up half as often and was not
-// behind at any batch size or ring measured.  A walk also bounds the state traffic: the hot part of a stream's block
-// is copied into LDS once per walk and written back once (ns_kernels1.hip, "the resident state block"), so C steps
-// move it once instead of C times, and seq[s] advances once per walk; C = 1 copies in and out around every step.
-constexpr int kFlowWalkAuto = 4;
+// Steps per workgroup of a pair-layout hand-off launch of a batch left on auto (AspNsBatch_SetFlowWalk and
+// ASP_NS_FLOW_WALK force a length): kFlowWalkLong when the batch has at least one workgroup (four streams) per compute
+// unit of its device, kFlowWalkShort for a smaller one.  Nothing else enters: no timing, no environment.
+// Why: a walk pays the copy of the resident state block in and out, the drain, the publish of seq[s], the exit skew of
+// the workgroup's four waves and the successor's dispatch and set-up once (ns_kernels1.hip), so longer walks save;
+// but the last round of workgroups of a launch is as long as a walk, and a nearly empty one (4100 streams: 1025
+// workgroups on 1024 slots) idles the chip for that long, and from 32 steps up the chip is back in one phase.  8 is
+// the one length measured ahead of or level with 4 in every cell -- 1024 to 16384 streams, ring 100 and 20, 1000-step
+// and 20-step regions; 16 is 0.3 us behind at 4100 streams.  The launch length was measured (20-step launches: two
+// walks of 8 and one of 4) and does not enter.  The boundary is the smallest size measured, not a boundary that was
+// found: 1024 and 2048 streams gain more than the sizes that fill the device, nothing smaller was measured, and
+// tests/test_ns_walk_gpu.py pins 4 for 5 streams.  Tables and the cells: profiles/README.md, first section.
+// The wait this bounds: a chunk's first step waits for its predecessor's walk, which is resident or done by then
+// (workgroups are dispatched in grid order): at most walk x the step time of a wave x the batches sharing the chip,
+// 8 x ~10 us x, say, 16 batches = ~1.3 ms, and ~10 ms for a forced walk of 64 -- two orders and one order of
+// magnitude under kHandoffSpinLimit (handoff.h, ~0.1 s), which stays as it is.
+constexpr int kFlowWalkShort = 4;
+constexpr int kFlowWalkLong = 8;
+static int flow_walk_auto(int streams, int compute_units) {
+  return (streams + 3) / 4 >= compute_units ? kFlowWalkLong : kFlowWalkShort;
+}
 
 // K steps of the hand-off build on the batch's stream: launches of up to kHandoffMaxSteps consecutive frame
-// steps each (pair-layout kernel: grid y = chunk of steps, kFlowWalkAuto; kernel 2: grid y = step); launches follow
+// steps each (pair-layout kernel: grid y = chunk of steps, flow_walk_auto; kernel 2: grid y = step); launches follow
 // each other in stream order.
 static int flow_steps(AspNsBatch* b, const float* din, float* dout, int ring, int steps, bool io16) {
   HIP_TRY(b->sync.ensure(b->S, b->stream));
@@ -858,19 +879,24 @@ static int flow_steps(AspNsBatch* b, const float* din, float* dout, int ring, in
     const int v = atoi(e);
     if (v >= 2 && v <= kHandoffMaxSteps) maxm = v;
   }
-  int walk = b->flow_walk != 0 ? b->flow_walk : kFlowWalkAuto;
+  int walk = b->flow_walk;
   if (b->flow_walk == 0)
     if (const char* e = getenv("ASP_NS_FLOW_WALK")) {  // tuning: steps per workgroup of batches left on auto
       const int v = atoi(e);
       if (v >= 1 && v <= kHandoffMaxSteps) walk = v;  // (anything else is ignored, as the setter would refuse it)
     }
+  if (walk == 0 && b->kernel != 2 && b->flow_cus == 0) {  // once per batch
+    HIP_TRY(hipDeviceGetAttribute(&b->flow_cus, hipDeviceAttributeMultiprocessorCount, b->device));
+    if (b->flow_cus < 1) b->flow_cus = 1;
+  }
   for (int k = 0; k < steps; k += maxm) {
     const int m = steps - k < maxm ? steps - k : maxm;
     if (b->kernel == 2)
       HIP_TRY(launch_ns_frame2_flow(io16, b->state, b->hist, b->tables, din, dout, b->S, b->stream, b->sync.seq,
                                     b->sync.abort, b->sync.count, m, k % ring, ring, per, b->flow_stamps));
     else {
-      const int w = walk < m ? walk : m;
+      const int wa = walk != 0 ? walk : flow_walk_auto(b->S, b->flow_cus);
+      const int w = wa < m ? wa : m;
       HIP_TRY(launch_ns_frame1_flow(io16, b->state, b->hist, b->tables, din, dout, b->S, b->stream, b->sync.seq,
                                     b->sync.abort, b->sync.count, m, w, k % ring, ring, per, b->flow_stamps));
       b->flow_chunks = (m + w - 1) / w;

@@ -68,8 +68,11 @@ __device__ __forceinline__ const P* ns_cold(const P* p) {  // (a wave-uniform po
 // walk) - 1 of its four streams, one after the other.  What does not change from step to step -- the tables in LDS and
 // the one barrier behind them, the lane constants, the stream's buffer descriptor -- is set up once per chunk, and only
 // the chunk's first step waits for a counter.  walk == 1 is one step per workgroup; walk == steps leaves no dependency
-// between workgroups at all -- and every wave of the chip in the same phase again: short walks measured fastest
-// (ns_api.hip, flow_walk).
+// between workgroups at all -- and every wave of the chip in the same phase again.  The host sizes the walk to the
+// launch (ns_api.hip, flow_walk_auto): 8 steps for a batch with at least one workgroup per compute unit, 4 for a smaller
+// one -- every chunk boundary costs the image's write-back, the drain, the publish, the exit skew of the workgroup's
+// four waves and the successor's set-up and copy-in, which the resident state block below made the larger part of what
+// a walk saves; 16 steps and more lose again where the last round of workgroups is ragged (profiles/README.md).
 //
 // The resident state block: nobody else may touch a stream's state before its walk ends, so the hot part of the block
 // -- its first kImgDwords dwords in ns_layout.h order: scalars and row tails, both sliding-buffer carries, rows V_LQ0 ..

@@ -88,6 +88,7 @@ def load_library():
         "AspNs_rdft256_batch": [vp, ip, ip, ip, ip],
         "AspNs_rdft128_batch": [vp, ip, ip, ip, ip],
         "AspNs_device_count": [],
+        "AspNs_device_compute_units": [ip, C.POINTER(C.c_int)],
     }
     _declare(lib, sig)
     lib.AspNsBatch_GetStream.argtypes = [vp]
@@ -113,6 +114,13 @@ def copy_ceiling_gbs(nbytes=1 << 30, iters=8, device=0):
 def device_count():
     n = load_library().AspNs_device_count()
     return max(n, 0)
+
+
+def device_compute_units(device=0):
+    """hipDeviceProp_t::multiProcessorCount of `device`: what the automatic walk length is sized by (asp_ns.h)."""
+    n = C.c_int(0)
+    _check(load_library().AspNs_device_compute_units(device, C.byref(n)), "AspNs_device_compute_units")
+    return n.value
 
 
 def _ptr(a):

@@ -199,9 +199,11 @@ int AspNsBatch_SetKernel(AspNsBatch* b, int kernel);
 int AspNsBatch_SetFlow(AspNsBatch* b, int mode);
 /* Hand-off build, pair-layout kernel: how many consecutive frame steps of a launch one workgroup walks for its four
  * streams (tables, barrier and lane set-up once per walk; only the walk's first step waits for a counter).
- * 0 = auto (4 steps: short walks measured fastest, the whole launch puts every wave of the chip in the same
- * phase); 1..64 force a length (the environment variable ASP_NS_FLOW_WALK does the same for batches left on
- * auto).  Same results bit for bit for every value. */
+ * 0 = auto, sized to the launch: 8 steps when the batch has at least one workgroup (four streams) per compute unit
+ * of its device -- ceil(num_streams / 4) >= hipDeviceProp_t::multiProcessorCount, 1024 streams on an MI355X -- and 4
+ * steps for a smaller batch; a launch shorter than that is one walk.  The rule looks at nothing else (why 8, and why
+ * that boundary: the comment above flow_walk_auto in csrc/ns_api.hip).  1..64 force a length (the environment variable
+ * ASP_NS_FLOW_WALK does the same for batches left on auto).  Same results bit for bit for every value. */
 int AspNsBatch_SetFlowWalk(AspNsBatch* b, int steps);
 /* Test hook: the grid's y extent (chunks of steps = ceil(steps / walk)) of the batch's last hand-off launch of the
  * pair-layout kernel; 0 before the first one. */
@@ -246,6 +248,9 @@ int AspNsBatch_LastEnqueueUs(AspNsBatch* b, double* us);
 
 /* Number of HIP devices visible, or a negative error code. */
 int AspNs_device_count(void);
+/* Compute units of HIP device `device` (hipDeviceProp_t::multiProcessorCount): what AspNsBatch_SetFlowWalk's
+ * automatic length is sized by. */
+int AspNs_device_compute_units(int device, int* compute_units);
 /* Text of the most recent failure on this thread ("" if none).  The record is library-wide: a failure
    of any module (NS, BT, AEC, split, resample, VAD, AECM, NSX) overwrites it. */
 const char* AspNs_last_error(void);

@@ -27,12 +27,13 @@ namespace aspns {
 hipError_t launch_ns_frame(int mode, float* state, int32_t* hist, const NsTables* T,
                            const float* in, float* out, int num_streams, hipStream_t s, bool g8 = false);
 hipError_t launch_ns_frame1(bool io16, float* state, int32_t* hist, const NsTables* T,
-                            const float* in, float* out, int num_streams, hipStream_t s,
-                            unsigned long long* stamps = nullptr, int stamp_mode = 0);
+                            const float* in, float* out, int num_streams, hipStream_t s, int steady_on,
+                            unsigned long long* stamps = nullptr, int stamp_mode = 0, unsigned* step_counts = nullptr);
 hipError_t launch_ns_frame1_flow(bool io16, float* state, int32_t* hist, const NsTables* T,
                                  const float* in, float* out, int num_streams, hipStream_t s,
                                  unsigned* seq, unsigned* abort_w, unsigned want, int steps, int walk, int slot0,
-                                 int ring, size_t per, unsigned long long* stamps = nullptr);
+                                 int ring, size_t per, int steady_on, unsigned long long* stamps = nullptr,
+                                 unsigned* step_counts = nullptr);
 hipError_t launch_ns_frame2(bool io16, float* state, int32_t* hist, const NsTables* T,
                             const float* in, float* out, int num_streams, hipStream_t s,
                             unsigned long long* stamps = nullptr);
@@ -596,6 +597,11 @@ struct AspNsBatch {
   // its first hand-off call).
   int flow_cus = 0;
   int flow_chunks = 0;  // grid y of the last such launch (AspNsBatch_DebugFlowChunks)
+  // Pair-layout kernel: steps of a stream in steady state take the steady body of the frame step (ns_kernels1.hip,
+  // ns_step_is_steady).  -1 = default (on; ASP_NS_STEADY=0 turns the default off), 0 = off (every step through the
+  // generic body), 1 = on.  Same results bit for bit.
+  int steady = -1;
+  unsigned* step_counts = nullptr;  // diagnostic (AspNsBatch_DebugStepCounts): [S][2] steady / generic steps
   HandoffSync sync;
   // > 16 kHz: 1 or 2 high bands next to the low band (ns_core.c:1362-1414)
   uint32_t fs = 16000;
@@ -693,6 +699,7 @@ int AspNsBatch_Free(AspNsBatch* b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->state) (void)hipFree(b->state);
   if (b->hist) (void)hipFree(b->hist);
+  if (b->step_counts) (void)hipFree(b->step_counts);
   b->sync.release();
   b->stage_in.release();
   b->stage_out.release();
@@ -813,6 +820,11 @@ int AspNsBatch_set_policy(AspNsBatch* b, int mode) {
   return ASP_OK;
 }
 
+// The kernel argument that is ANDed into the steady-state predicate of the pair-layout frame step.
+static int steady_arg(const AspNsBatch* b) {
+  return (b->steady < 0 ? handoff_env_default("ASP_NS_STEADY") : b->steady != 0) ? 1 : 0;
+}
+
 // One fused paired frame step over streams [s0, s0 + n) of the batch.
 static hipError_t fused_launch(AspNsBatch* b, bool io16, const float* din, float* dout, int s0, int n,
                                hipStream_t st) {
@@ -827,7 +839,8 @@ static hipError_t fused_launch(AspNsBatch* b, bool io16, const float* din, float
     return launch_ns_frame2(io16, state, hist, b->tables, in, out, n, st);
   // timeline diagnostic: this sub-launch's first workgroup's slot, stamp mode 1
   unsigned long long* tl = b->timeline ? b->timeline + (size_t)(s0 / 4) * 4 : nullptr;
-  return launch_ns_frame1(io16, state, hist, b->tables, in, out, n, st, tl, tl ? 1 : 0);
+  unsigned* sc = b->step_counts ? b->step_counts + (size_t)s0 * 2 : nullptr;
+  return launch_ns_frame1(io16, state, hist, b->tables, in, out, n, st, steady_arg(b), tl, tl ? 1 : 0, sc);
 }
 
 // stream boundaries of the sub-launch chains: multiples of 8 streams (two workgroups of 4)
@@ -898,7 +911,8 @@ static int flow_steps(AspNsBatch* b, const float* din, float* dout, int ring, in
       const int wa = walk != 0 ? walk : flow_walk_auto(b->S, b->flow_cus);
       const int w = wa < m ? wa : m;
       HIP_TRY(launch_ns_frame1_flow(io16, b->state, b->hist, b->tables, din, dout, b->S, b->stream, b->sync.seq,
-                                    b->sync.abort, b->sync.count, m, w, k % ring, ring, per, b->flow_stamps));
+                                    b->sync.abort, b->sync.count, m, w, k % ring, ring, per, steady_arg(b), b->flow_stamps,
+                                    b->step_counts));
       b->flow_chunks = (m + w - 1) / w;
     }
     b->sync.enqueued(m);
@@ -917,6 +931,10 @@ static int flow_check(AspNsBatch* b) {
 // `steps` fused frame steps on device buffers; step k reads/writes ring slot k % ring.
 static int fused_steps(AspNsBatch* b, const float* din, float* dout, int ring, int steps,
                        bool io16 = false) {
+  // the diagnostic kernels of the pair-layout step exist for float frames only: refuse here, with a reason
+  if (io16 && (b->step_counts || b->timeline || b->flow_stamps) && b->kernel != 1 && b->kernel != 2 && b->fs != 8000)
+    return fail(ASP_ERR_STATE, "int16 frames while a diagnostic of the pair-layout kernel (step counts, timeline, stamps) "
+                               "is on: the diagnostic kernels take float frames; switch it off first");
   if (flow_applies(b, steps)) return flow_steps(b, din, dout, ring, steps, io16);
   // offsets below are in float units; int16 frames are half as wide
   const size_t per = (size_t)b->S * b->block / (io16 ? 2 : 1);
@@ -1349,7 +1367,7 @@ int AspNsBatch_DebugStamps(AspNsBatch* b, const float* in_dev, float* out_dev,
   HIP_TRY(hipMalloc((void**)&d, 16 * sizeof(unsigned long long)));
   hipError_t e = hipMemset(d, 0, 16 * sizeof(unsigned long long));
   if (e == hipSuccess)
-    e = launch_ns_frame1(false, b->state, b->hist, b->tables, in_dev, out_dev, b->S, b->stream, d);
+    e = launch_ns_frame1(false, b->state, b->hist, b->tables, in_dev, out_dev, b->S, b->stream, steady_arg(b), d);
   if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
   if (e == hipSuccess) e = hipMemcpy(stamps16, d, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
   (void)hipFree(d);
@@ -1419,6 +1437,33 @@ int AspNsBatch_LastEnqueueUs(AspNsBatch* b, double* us) {
 int AspNsBatch_SetFlow(AspNsBatch* b, int mode) {
   if (!b || mode < -1 || mode > 1) return fail(ASP_ERR_PARAM, "SetFlow: -1 (default), 0 (off) or 1 (on)");
   b->flow = mode;
+  return ASP_OK;
+}
+
+int AspNsBatch_SetSteady(AspNsBatch* b, int on) {
+  if (!b || on < -1 || on > 1) return fail(ASP_ERR_PARAM, "SetSteady: -1 (default), 0 (off) or 1 (on)");
+  b->steady = on;
+  return ASP_OK;
+}
+
+// Diagnostic (tests only): from now on the pair-layout launches of the batch (float frames) run the diagnostic
+// kernels and count, per stream, the frame steps that took the steady body and the generic one; `counts` ([S][2],
+// host) receives the sums so far.  on = 0 frees the buffer and returns to the product kernels.
+int AspNsBatch_DebugStepCounts(AspNsBatch* b, int on, unsigned* counts) {
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
+  if (rc) return rc;
+  const size_t bytes = (size_t)b->S * 2 * sizeof(unsigned);
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (on && !b->step_counts) {
+    HIP_TRY(hipMalloc((void**)&b->step_counts, bytes));
+    HIP_TRY(hipMemset(b->step_counts, 0, bytes));
+  }
+  if (counts && b->step_counts) HIP_TRY(hipMemcpy(counts, b->step_counts, bytes, hipMemcpyDeviceToHost));
+  if (!on && b->step_counts) {
+    HIP_TRY(hipFree(b->step_counts));
+    b->step_counts = nullptr;
+  }
   return ASP_OK;
 }
 

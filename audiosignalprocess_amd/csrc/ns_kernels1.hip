@@ -25,6 +25,8 @@
 //     ASP_NS_REDUCE_TREE64P and the tests compare bit for bit (outputs and every state array).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "handoff.h"
 #include "ns_device.h"
 #include "ns_layout.h"
@@ -43,6 +45,14 @@ __device__ __forceinline__ unsigned long long ns_cu_tag() {
 }
 
 constexpr int NS3 = 3;  // 2 owned bins + the tail bin 128
+
+// A wave-uniform value parked in a vector register: the diagnostic kernels keep their few extra words there, because
+// the step loop of the hand-off build has no scalar register to spare (SGPR spills) and a few vector ones.
+template <typename V>
+__device__ __forceinline__ V ns_in_vgpr(V x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
 
 // A copy of a lane constant that the compiler cannot see through.  The rarely taken paths of the frame step (start-up,
 // histogram window) derive addresses, masks and fp64 values from the lane index; in the step loop of the hand-off build
@@ -187,49 +197,114 @@ struct StateAcc {
   }
 };
 
-template <bool IO16, bool FLOW>
-__global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ state,
-                                                           int32_t* __restrict__ hist_all,
-                                                           const NsTables* __restrict__ T,
-                                                           const float* __restrict__ in,
-                                                           float* __restrict__ out,
-                                                           int num_streams,
-                                                           unsigned long long* __restrict__ stamps,
-                                                           int stamp_mode, NsFlowArgs fa) {
+// ---- the two bodies of a frame step.  From the point where the step has read its wave-uniform scalars, the rest of
+// the step exists twice, generated from ONE source text (the generic lambda `step_rest` below): the generic body, which
+// serves every state a stream can be in, and the steady body, compiled under the assumption that the stream is past
+// both start-up windows, that no quantile tracker publishes in this step, that the histogram window stays open and
+// that gain compensation is on -- all but 6 steps in 200 and 2 in 500 of a long-running stream.  ONE predicate chooses per
+// step, ns_step_is_steady(); the assumes of the steady body (ns_assume_steady) are expanded from the same list of
+// conjuncts, NS_STEADY_CONJUNCTS, so the two cannot drift apart: a wrong assume is undefined behaviour, not a slow
+// path.  Only wave-uniform scalars of the scalar row enter; nothing is assumed about data (the frame's energy, the
+// libm fallbacks, per-lane branches).  Both bodies put every value through the same operations in the same order.
+struct NsStepScalars {
+  int blockInd;        // of this step: already incremented (ns_core.c:1084)
+  int updates;
+  int counter[3];
+  int updateParsFlag;
+  int mup3;            // frames left in the histogram window, before this step's decrement
+  int gainmap;
+};
+#define NS_STEADY_CONJUNCTS(X, s)                                                                                   \
+  X((s).blockInd > NS_END_STARTUP_LONG + 1)                             /* past both start-up windows */              \
+  X((s).updates >= NS_END_STARTUP_LONG)                                                                              \
+  X((s).counter[0] < NS_END_STARTUP_LONG - 1 && (s).counter[1] < NS_END_STARTUP_LONG - 1 &&                           \
+    (s).counter[2] < NS_END_STARTUP_LONG - 1)                           /* no tracker at or next to its publish */    \
+  X((s).counter[0] >= 0 && (s).counter[1] >= 0 && (s).counter[2] >= 0)                                                \
+  X((s).updateParsFlag >= 1)                                                                                         \
+  X((s).mup3 > 2)                                                       /* the histogram window stays open */         \
+  X((s).gainmap == 1)
+__device__ __forceinline__ bool ns_step_is_steady(const NsStepScalars& s) {
+  bool steady = true;
+#define NS_CONJ_AND(c) steady = steady && (c);
+  NS_STEADY_CONJUNCTS(NS_CONJ_AND, s)
+#undef NS_CONJ_AND
+  return steady;
+}
+__device__ __forceinline__ void ns_assume_steady(const NsStepScalars& s) {
+#define NS_CONJ_ASSUME(c) __builtin_assume(c);
+  NS_STEADY_CONJUNCTS(NS_CONJ_ASSUME, s)
+#undef NS_CONJ_ASSUME
+}
+
+// diagnostics of the DIAG instantiations (never passed by the product entry points, whose kernels have no such code)
+struct NsDiagArgs {
+  void* buf;  // ONE buffer, so that the step loop carries one pointer: stamps (unsigned long long) or step counts
+  int mode;   // 0 = the phase stamps, 1 = the timeline (both below), 2 = step counts: [stream][2] unsigned, the steps
+              // that took the steady body and the generic body, added up
+};
+
+// The frame step.  DIAG: the diagnostic stamps and the per-stream step counts exist (ns_frame1_diag_kernel); the
+// product kernels (ns_frame1_kernel) are the DIAG = false instantiations, where NS_STAMP expands to nothing.
+// steady_on: 0 routes every step through the generic body (AspNsBatch_SetSteady, A / B runs and tests).
+template <bool IO16, bool FLOW, bool DIAG>
+__device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t* __restrict__ hist_all,
+                                              const NsTables* __restrict__ T, const float* __restrict__ in,
+                                              float* __restrict__ out, int num_streams, int steady_on,
+                                              const NsFlowArgs& fa, const NsDiagArgs& dg) {
+  // the diagnostic buffer (the hand-off build parks its address in a vector register pair: ns_in_vgpr)
+  [[maybe_unused]] const unsigned long long diag_buf =
+      DIAG ? (FLOW ? ns_in_vgpr((unsigned long long)dg.buf) : (unsigned long long)dg.buf) : 0ull;
 #ifdef NS1_BUDGET
-  // instruction-budget build (tools/ns_valu_budget.py, never shipped): the phase marks become
-  // assembly comments and the steady-state conditions are asserted, so that the straight-line
-  // code between two marks is what a wave executes per frame after start-up
-#define NS_STAMP(k)                                                                \
-  __builtin_amdgcn_sched_barrier(0);                                               \
-  asm volatile("; NS_PHASE " #k);                                                  \
-  __builtin_amdgcn_sched_barrier(0);
-#define NS_STEADY(x) __builtin_assume(x)
+  // instruction-budget build (tools/ns_valu_budget.py, never shipped): the product code with the phase marks as
+  // assembly comments and nothing else changed; a mark names the body it stands in (0 shared, 1 steady, 2 generic, 3 aside)
+#define NS_STAMP(k) asm volatile("; NS_PHASE " #k " body %0" : : "n"(ns_body_tag));
+  // blocks a steady step does not execute (the zero-energy exit, the walk's end, the set-up in front of the loop) are
+  // bracketed: body 3 from NS_BUDGET_ASIDE to the NS_BUDGET_BACK(k) that names the phase and body it returns to
+#define NS_BUDGET_ASIDE() asm volatile("; NS_PHASE 99 body 3");
+#define NS_BUDGET_BACK(k) asm volatile("; NS_PHASE " #k " body %0" : : "n"(ns_body_tag));
 #else
-  // diagnostic stamps (never passed by the product entry points).  stamp_mode 0: the 16 phase stamps
+  // diagnostic stamps.  stamp_mode 0: the 16 phase stamps
   // (shader clock) of workgroup 0's first wave (hand-off build: of the middle of the launch, x = grid / 2,
   // step = steps / 2, plus a 17th at that step's end: once its stores have drained where it is its walk's last).  stamp_mode 1 ("timeline"): every workgroup's first
   // wave records the 100 MHz real-time counter at its start, after its first loads, before its last
   // stores and at its end (4 values per workgroup) -- the launch-level picture.
-  // (one wave-uniform word decides: the stamps cost the step loop of the hand-off build one scalar register)
-  const int stamp_on = (stamps != nullptr && threadIdx.x < 64) ? (stamp_mode != 0 ? 1 : 2) : 0;
-#define NS_STAMP(k)                                                                          \
-  if (__builtin_amdgcn_readfirstlane(stamp_on) != 0 && threadIdx.x == 0) {                   \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-    if (stamp_on == 1) {                                                                     \
-      if ((k) == 0 || (k) == 1 || (k) == 14 || (k) == 15)                                    \
-        stamps[blockIdx.x * 4 + ((k) == 0 ? 0 : (k) == 1 ? 1 : (k) == 14 ? 2 : 3)] =        \
-            __builtin_amdgcn_s_memrealtime() | ((k) == 0 ? ns_cu_tag() << 48 : 0ull);       \
-    } else if (FLOW ? (blockIdx.x == gridDim.x / 2 && flow_j == fa.steps / 2)                \
-                    : blockIdx.x == 0) {                                                     \
-      stamps[k] = __builtin_amdgcn_s_memtime();                                              \
-    }                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
+  // One wave-uniform word decides: 0 = this wave takes no stamp, 1 = the timeline, 2 + j = the phase stamps, in step j
+  // of the launch (the plain build: j = 0).  The DIAG kernels must hold the register budget of the product kernels
+  // (tests/test_ns_steady_host.py), so a stamp point keeps nothing else alive: the buffer comes from `dg` where it is
+  // written.
+  [[maybe_unused]] unsigned stamp_sel = 0;
+  if constexpr (DIAG) {
+    if (dg.buf != nullptr && dg.mode != 2 && threadIdx.x < 64) {
+      if (dg.mode == 1) stamp_sel = 1u;
+      else if (FLOW ? blockIdx.x == gridDim.x / 2 : blockIdx.x == 0) stamp_sel = 2u + (FLOW ? fa.steps / 2 : 0u);
+    }
   }
-#define NS_STEADY(x)
+  // (a scalar branch only: every lane of the stamping wave stores the same value to the same address)
+#define NS_STAMP(k)                                                                            \
+  if constexpr (DIAG) {                                                                        \
+    const unsigned stamp_sel_ = __builtin_amdgcn_readfirstlane(stamp_sel);                     \
+    if (stamp_sel_ != 0) {                                                                     \
+      __builtin_amdgcn_sched_barrier(0);                                                       \
+      unsigned long long* const stamps_ = reinterpret_cast<unsigned long long*>(diag_buf);     \
+      if (stamp_sel_ == 1u) {                                                                  \
+        if ((k) == 0 || (k) == 1 || (k) == 14 || (k) == 15)                                    \
+          stamps_[blockIdx.x * 4 + ((k) == 0 ? 0 : (k) == 1 ? 1 : (k) == 14 ? 2 : 3)] =       \
+              __builtin_amdgcn_s_memrealtime() | ((k) == 0 ? ns_cu_tag() << 48 : 0ull);       \
+      } else if (stamp_sel_ == 2u + flow_j) {                                                  \
+        stamps_[k] = __builtin_amdgcn_s_memtime();                                             \
+      }                                                                                        \
+      __builtin_amdgcn_sched_barrier(0);                                                       \
+    }                                                                                          \
+  }
+#define NS_BUDGET_ASIDE()
+#define NS_BUDGET_BACK(k)
 #endif
   // the hand-off build's chunk of the launch: steps flow_j .. flow_end - 1; step flow_j uses ring slot flow_slot
   unsigned flow_j = 0, flow_end = 1, flow_slot = 0;
+  // DIAG: the steps of this walk that took the steady body (low half) and the generic one (high half: a walk has at
+  // most 64 steps), added to the stream's two counts when the wave is done
+  [[maybe_unused]] unsigned diag_steps = 0;
+  [[maybe_unused]] constexpr int ns_body_tag = 0;  // (budget build: the marks outside the two bodies)
   if constexpr (FLOW) {
     flow_j = blockIdx.y * fa.walk;
     flow_end = flow_j + fa.walk < fa.steps ? flow_j + fa.walk : fa.steps;
@@ -270,6 +345,15 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
   int32_t* __restrict__ hist = hist_all + (size_t)stream * kHistDwords;
   const StateAcc<FLOW> sa(st, FLOW ? imgs[wv] : nullptr);
   float* outj = out;  // this step's frame of `out` (hand-off build: its ring slot)
+  auto diag_flush_steps = [&]() __attribute__((always_inline)) {
+    if constexpr (DIAG) {
+      unsigned* const counts = reinterpret_cast<unsigned*>(diag_buf);
+      if (dg.mode == 2 && ns_cold(lane) == 0) {
+        atomicAdd(counts + 2 * stream, diag_steps & 0xffffu);
+        atomicAdd(counts + 2 * stream + 1, diag_steps >> 16);
+      }
+    }
+  };
 
   // ---- scalars: lane k holds scalar k (wave-uniform values, read with v_readlane)
   float sv;
@@ -297,7 +381,10 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
   };
   // hand-off build: the first state reads of step flow_j, from the image (the scalar row is read once per walk and
   // stays in `sv` between the walk's steps)
-  auto flow_head = [&]() __attribute__((always_inline)) {
+  // (head_c: the budget build's body tag of this copy of the head -- 0 where a step that goes on executes it, 3 for
+  // the copy in front of the loop and the one behind the zero-energy exit)
+  auto flow_head = [&](auto head_c) __attribute__((always_inline)) {
+    [[maybe_unused]] constexpr int ns_body_tag = decltype(head_c)::value;
     NS_STAMP(0)
     outj = out + (size_t)flow_slot * fa.per;
     const int lane_c = ns_cold(lane);
@@ -349,7 +436,7 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
   if (!wave_live) return;
   if constexpr (FLOW) {
     sv = sa.ld1(kOffScalars, lane);
-    flow_head();
+    flow_head(std::integral_constant<int, 3>{});
   }
   const float* tws = tabs;
   const float* spls = tabs + 3 * 64 * 4;
@@ -376,10 +463,12 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
   // the step is done for this stream.  Hand-off build: after the walk's last step the wave writes its image back,
   // drains every store it has issued and publishes the walk; otherwise it goes on to its next step on the image (the
   // wave-level fence orders this step's image writes, other lanes' too, in front of the next step's reads)
-#define NS_STREAM_DONE()                                                                       \
+#define NS_STREAM_DONE(head_tag)                                                               \
   if constexpr (FLOW) {                                                                        \
+    [[maybe_unused]] constexpr int ns_body_tag = head_tag; /* (budget build: where this copy stands) */ \
     const bool walk_done_ = flow_j + 1u >= flow_end;                                           \
     if (walk_done_) {                                                                          \
+      NS_BUDGET_ASIDE()                                                                        \
       const int lane_w_ = ns_cold(lane);                                                       \
       sa.st1(kOffScalars, lane_w_, sv);                                                        \
       lds_sync1();                                                                             \
@@ -388,18 +477,23 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
     }                                                                                          \
     NS_STAMP(16)                                                                               \
     if (walk_done_) {                                                                          \
+      NS_BUDGET_ASIDE()                                                                        \
+      diag_flush_steps();                                                                      \
       if (lane == 0) handoff_publish(fa.hand.seq + stream, fa.want + flow_j);                  \
       return;                                                                                  \
     }                                                                                          \
     ++flow_j;                                                                                  \
     lds_sync1();                                                                               \
-    flow_head();                                                                               \
+    NS_BUDGET_BACK(16)                                                                         \
+    flow_head(std::integral_constant<int, head_tag>{});                                        \
     continue;                                                                                  \
   } else {                                                                                     \
+    diag_flush_steps();                                                                        \
     return;                                                                                    \
   }
 
   for (;;) {  // the steps of the chunk (one pass in the plain build); no barrier inside: each wave owns its LDS tile
+    NS_BUDGET_BACK(0)
     // state rows are requested in two groups, just ahead of their use (requesting all of them before
     // the first wait measured slower: every wave of a launch starts at once, and a bigger
     // start-of-kernel burst makes every wave wait longer)
@@ -422,8 +516,8 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
       if (lane_c >= 40) sa.st4(kOffAnaHist, 4 * (lane_c - 40), s4);
     }
 
-    NS_STEADY(energy1 != 0.0f);
     if (energy1 == 0.0f) {
+      NS_BUDGET_ASIDE()
       // Analyze: nothing but the buffer slide (ns_core.c:1072-1082); Process: emit the synthesis
       // tail and clear it (ns_core.c:1239-1264)
       float* y = IO16 ? reinterpret_cast<float*>(reinterpret_cast<short*>(outj) + (size_t)stream * kBlockL)
@@ -436,8 +530,9 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
       store2p<IO16>(y, 2 * lane_c, sat16p(o01.x), sat16p(o01.y));
       if (lane_c < 16) store2p<IO16>(y, 128 + 2 * lane_c, 0.f, 0.f);
       if (lane_c < 48) sa.st2(kOffSynt, 2 * lane_c, 0.f, 0.f);
-      NS_STREAM_DONE()
+      NS_STREAM_DONE(3)
     }
+    NS_BUDGET_BACK(0)
 
     // the tracker rows are requested once the frame's samples are in; they are used after the
     // transform, the magnitudes and the logarithms
@@ -485,570 +580,585 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
     // 64 partials, then bin 128 (association ASP_NS_REDUCE_TREE64P of oracle/ns_oracle.c)
 #define SUM3(v) (wave_sum_bcast(v[0] + v[1]) + v[2])
 
-    int blockInd = SC_I(S_BLOCKIND);
-    const float overdrive = SC_F(S_OVERDRIVE);
-    const float denoiseBound = SC_F(S_DENOISEBOUND);
-    float priorSpeechProb = SC_F(S_PRIORSPEECHPROB);
-    const int gainmap = SC_I(S_GAINMAP);
+    // the wave-uniform scalars that decide which body serves the step, and the decision
+    NsStepScalars ss;
+    ss.blockInd = SC_I(S_BLOCKIND) + 1;  // ns_core.c:1084
+    ss.updates = SC_I(S_UPDATES);
+    ss.counter[0] = SC_I(S_COUNTER0);
+    ss.counter[1] = SC_I(S_COUNTER1);
+    ss.counter[2] = SC_I(S_COUNTER2);
+    ss.updateParsFlag = SC_I(S_MUP0);
+    ss.mup3 = SC_I(S_MUP3);
+    ss.gainmap = SC_I(S_GAINMAP);
+    const bool step_steady = steady_on != 0 && ns_step_is_steady(ss);
+    // ---- the rest of the step, up to the commit of its scalars: ONE text, instantiated as the steady body
+    // (steady_c = std::true_type: under the assumes of ns_assume_steady) and as the generic one.  It is a lambda: a
+    // `return` inside would leave the lambda and not the kernel, and `continue` is not available; the step ends
+    // behind the two calls below, in NS_STREAM_DONE.
+    auto step_rest = [&](auto steady_c) __attribute__((always_inline)) {
+      constexpr bool STEADY = decltype(steady_c)::value;
+      [[maybe_unused]] constexpr int ns_body_tag = STEADY ? 1 : 2;
+      if constexpr (STEADY) ns_assume_steady(ss);
+      if constexpr (DIAG) diag_steps += STEADY ? 1u : 0x10000u;
+      const int blockInd = ss.blockInd;
+      const float overdrive = SC_F(S_OVERDRIVE);
+      const float denoiseBound = SC_F(S_DENOISEBOUND);
+      float priorSpeechProb = SC_F(S_PRIORSPEECHPROB);
+      const int gainmap = ss.gainmap;
 
-    float noise[NS3], prevStsa[NS3];
-    blockInd++;  // ns_core.c:1084
-    const int updateParsFlag = SC_I(S_MUP0);
-    int updates = SC_I(S_UPDATES);
-    int counter[3] = {SC_I(S_COUNTER0), SC_I(S_COUNTER1), SC_I(S_COUNTER2)};
-    // steady state (budget build only): past both start-up windows, no tracker publishes, the
-    // histogram window stays open, gain compensation on
-    NS_STEADY(blockInd > NS_END_STARTUP_LONG + 1);
-    NS_STEADY(updates >= NS_END_STARTUP_LONG);
-    NS_STEADY(counter[0] < NS_END_STARTUP_LONG - 1 && counter[1] < NS_END_STARTUP_LONG - 1 && counter[2] < NS_END_STARTUP_LONG - 1);
-    NS_STEADY(counter[0] >= 0 && counter[1] >= 0 && counter[2] >= 0);
-    NS_STEADY(updateParsFlag >= 1);
-    NS_STEADY(gainmap == 1);
+      float noise[NS3], prevStsa[NS3];
+      const int updateParsFlag = ss.updateParsFlag;
+      int updates = ss.updates;
+      int counter[3] = {ss.counter[0], ss.counter[1], ss.counter[2]};
 
-    float lmagn[NS3];
-    log_f32_via_tab_n<NS3>(magn, lmagn, logts);
+      float lmagn[NS3];
+      log_f32_via_tab_n<NS3>(magn, lmagn, logts);
 
-    NS_STAMP(3)
-    // the four cross-bin sums that need only this frame's spectrum and the loaded rows, reduced side by
-    // side: signal energy (ns_core.c:1089-1103), sum of magnitudes, the flatness numerator (bins 1..128,
-    // :535-541) and the mean of magnAvgPause (:603-607)
-    float signalEnergy, sumMagn, flatNum, avgPauseMean;
-    {
-      float p_se = (re[0] * re[0] + im[0] * im[0]) + (re[1] * re[1] + im[1] * im[1]);
-      float p_sm = magn[0] + magn[1];
-      float p_fl = lane == 0 ? lmagn[1] : lmagn[0] + lmagn[1];
-      float p_ap = avgPause[0] + avgPause[1];
-      wave_sums_bcast(p_se, p_sm, p_fl, p_ap);
-      signalEnergy = p_se + (re[2] * re[2] + im[2] * im[2]);
-      sumMagn = p_sm + magn[2];
-      flatNum = p_fl + lmagn[2];
-      avgPauseMean = p_ap + avgPause[2];
-      signalEnergy = DIV129(signalEnergy);
-    }
-
-    NS_STAMP(4)
-    // ---- NoiseEstimation (ns_core.c:217-285)
-    if (updates < NS_END_STARTUP_LONG) updates++;
-    bool quant_new = false;
-    // Bin 128 of the three trackers: three independent chains with one formula, evaluated ONCE with tracker s on
-    // lane 48 + s -- where its lquantile tail already sits in the scalar row; its density tail, three lanes up in
-    // the same DPP row, comes down by one row shift, and n - 1 / n / 1 / n are built per lane from the three
-    // counters.  Every value goes through the operations of its own wave-uniform pass; the other lanes compute
-    // on whatever the row holds and are dropped by the masked merge.
-    constexpr int kLqLane = S_TAIL0 + V_LQ0, kDenLane = S_TAIL0 + V_DEN0;
-    static_assert(V_LQ1 == V_LQ0 + 1 && V_LQ2 == V_LQ0 + 2 && V_DEN1 == V_DEN0 + 1 && V_DEN2 == V_DEN0 + 2 &&
-                  kDenLane == kLqLane + 3 && kLqLane / 16 == (kDenLane + 2) / 16,
-                  "the tracker tails: three + three consecutive lanes of one DPP row");
-    float lqT = sv, denT = dpp_move<0x103>(sv);  // row_shl:3: lane L reads lane L + 3
-    float rcnt1v;
-    {
-      const int cntb = lanes3_bits<kLqLane>(counter[0], counter[1], counter[2]);
-      const float cntv = (float)cntb, cnt1v = (float)(cntb + 1);
-      rcnt1v = fdiv(1.f, cnt1v);  // == 1.f / cnt1 (cnt1 = 1 .. 201)
-      tracker_step1(lqT, denT, lmagn[2], cntv, cnt1v, rcnt1v);
-    }
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
+      NS_STAMP(3)
+      // the four cross-bin sums that need only this frame's spectrum and the loaded rows, reduced side by
+      // side: signal energy (ns_core.c:1089-1103), sum of magnitudes, the flatness numerator (bins 1..128,
+      // :535-541) and the mean of magnAvgPause (:603-607)
+      float signalEnergy, sumMagn, flatNum, avgPauseMean;
       {
-        const float cnt = (float)counter[s];
-        const float cnt1 = (float)(counter[s] + 1);
-        const float rcnt1 = lane_bcast(rcnt1v, kLqLane + s);
-        f32x2 lq = {LQ[s][0], LQ[s][1]}, den = {DEN[s][0], DEN[s][1]};
-        tracker_step2(lq, den, f32x2{lmagn[0], lmagn[1]}, cnt, cnt1, rcnt1);
-        LQ[s][0] = lq.x; LQ[s][1] = lq.y;
-        DEN[s][0] = den.x; DEN[s][1] = den.y;
+        float p_se = (re[0] * re[0] + im[0] * im[0]) + (re[1] * re[1] + im[1] * im[1]);
+        float p_sm = magn[0] + magn[1];
+        float p_fl = lane == 0 ? lmagn[1] : lmagn[0] + lmagn[1];
+        float p_ap = avgPause[0] + avgPause[1];
+        wave_sums_bcast(p_se, p_sm, p_fl, p_ap);
+        signalEnergy = p_se + (re[2] * re[2] + im[2] * im[2]);
+        sumMagn = p_sm + magn[2];
+        flatNum = p_fl + lmagn[2];
+        avgPauseMean = p_ap + avgPause[2];
+        signalEnergy = DIV129(signalEnergy);
       }
-      if (counter[s] >= NS_END_STARTUP_LONG) {
-        counter[s] = 0;
-        if (updates >= NS_END_STARTUP_LONG) {
-          LQ[s][2] = lane_bcast(lqT, kLqLane + s);  // the publish wants the tail wave-uniform
-          exp_f32_via_f64_n<NS3>(LQ[s], quant, exp2s);
-          quant_new = true;
-        }
-      }
-      counter[s]++;
-    }
-    if (updates < NS_END_STARTUP_LONG) {
-      LQ[2][2] = lane_bcast(lqT, kLqLane + 2);
-      exp_f32_via_f64_n<NS3>(LQ[2], quant, exp2s);
-      quant_new = true;
-    }
-#pragma unroll
-    for (int k = 0; k < NS3; ++k) noise[k] = quant[k];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) sa.st2(kOffVec + (V_LQ0 + s) * kVecStride, 2 * lane, LQ[s][0], LQ[s][1]);
-#pragma unroll
-    for (int s = 0; s < 3; ++s) sa.st2(kOffVec + (V_DEN0 + s) * kVecStride, 2 * lane, DEN[s][0], DEN[s][1]);
-    sv = mergelanes_vgpr<(7ull << kLqLane)>(sv, lqT);
-    sv = mergelanes_vgpr<(7ull << kDenLane)>(sv, dpp_move<0x113>(denT));  // row_shr:3: lane L reads lane L - 3
-    // the published quantile changes once in ~67 frames past start-up (a tracker publishes every 200
-    // frames, ns_core.c:262-270): its row is written back only then (wave-uniform branch)
-    if (quant_new) STORE3(V_QUANT, quant)
 
-    NS_STAMP(5)
-    // ---- startup noise model (ns_core.c:1091-1100, 1109-1162)
-    float whiteNoiseLevel = SC_F(S_WHITE);
-    float pinkNoiseNumerator = SC_F(S_PINKNUM);
-    float pinkNoiseExp = SC_F(S_PINKEXP);
-    float fd5 = SC_F(S_FD5);
-    const bool startup = blockInd < NS_END_STARTUP_SHORT;
-    if (startup) {
-      const int binA_c = ns_cold(binA);
-      const NsTables* Tc = ns_cold(T);
-      float lm3[NS3], lilm[NS3];
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) {
-        const int bin = k < 2 ? binA_c + 32 * k : 128;
-        const float li = Tc->logi[bin];
-        lm3[k] = bin >= NS_START_BAND ? lmagn[k] : 0.f;
-        lilm[k] = bin >= NS_START_BAND ? li * lmagn[k] : 0.f;
-      }
-      const float sum_log_magn = SUM3(lm3);
-      const float sum_log_i_log_magn = SUM3(lilm);
-      const float sum_log_i = Tc->sum_log_i, sum_log_i_square = Tc->sum_log_i_square;
-      whiteNoiseLevel += DIV129(sumMagn) * overdrive;
-      float tmpFloat1 = sum_log_i_square * ((float)(kBins - NS_START_BAND));
-      tmpFloat1 -= (sum_log_i * sum_log_i);
-      float tmpFloat2 = (sum_log_i_square * sum_log_magn - sum_log_i * sum_log_i_log_magn);
-      float tmpFloat3 = tmpFloat2 / tmpFloat1;
-      if (tmpFloat3 < 0.f) tmpFloat3 = 0.f;
-      pinkNoiseNumerator += tmpFloat3;
-      tmpFloat2 = (sum_log_i * sum_log_magn);
-      tmpFloat2 -= ((float)(kBins - NS_START_BAND)) * sum_log_i_log_magn;
-      tmpFloat3 = tmpFloat2 / tmpFloat1;
-      if (tmpFloat3 < 0.f) tmpFloat3 = 0.f;
-      if (tmpFloat3 > 1.f) tmpFloat3 = 1.f;
-      pinkNoiseExp += tmpFloat3;
-      float parametric_num = 0.f, parametric_exp = 0.f;
-      if (pinkNoiseExp > 0.f) {
-        parametric_num = (float)exp((double)(pinkNoiseNumerator / (float)(blockInd + 1)));
-        parametric_num *= (float)(blockInd + 1);
-        parametric_exp = pinkNoiseExp / (float)(blockInd + 1);
-      }
-      float pn[NS3];
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) {
-        const int bin = k < 2 ? binA_c + 32 * k : 128;
-        if (pinkNoiseExp == 0.f) {
-          pn[k] = whiteNoiseLevel;
-        } else {
-          const float use_band = (float)(bin < NS_START_BAND ? NS_START_BAND : bin);
-          pn[k] = (float)((double)parametric_num / pow((double)use_band, (double)parametric_exp));
-        }
-        noise[k] *= (blockInd);
-        const float t2 = pn[k] * (NS_END_STARTUP_SHORT - blockInd);
-        noise[k] += (t2 / (float)(blockInd + 1));
-        noise[k] /= NS_END_STARTUP_SHORT;
-      }
-      if constexpr (FLOW) {  // (a cold row: in memory, the lane's offset from the opaque copy)
-        sa.st2(kOffVec + V_PARAMNOISE * kVecStride, 2 * ns_cold(lane), pn[0], pn[1]);
-        SC_SET_F(S_TAIL0 + V_PARAMNOISE, pn[2]);
-      } else {
-        STORE3(V_PARAMNOISE, pn)
-      }
-    }
-    if (blockInd < NS_END_STARTUP_LONG) {  // ns_core.c:1165-1169
-      fd5 *= blockInd;
-      fd5 += signalEnergy;
-      fd5 /= (blockInd + 1);
-    }
-
-    NS_STAMP(6)
-    // ---- ComputeSnr (ns_core.c:566-588)
-    float snrLocPost[NS3], snrLocPrior[NS3];
-    {
-      float dn1[NS3], dn2[NS3], q1[NS3], q2[NS3];
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) {
-        dn1[k] = noisePrev[k] + 0.0001f;
-        dn2[k] = noise[k] + 0.0001f;
-      }
-      fdiv3(magnPrevA, dn1, q1);
-      fdiv3(magn, dn2, q2);  // used where magn > noise
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) {
-        const float previousEstimateStsa = q1[k] * smooth[k];
-        prevStsa[k] = previousEstimateStsa;
-        snrLocPost[k] = 0.f;
-        if (magn[k] > noise[k]) snrLocPost[k] = q2[k] - 1.f;
-        snrLocPrior[k] = NS_DD_PR_SNR * previousEstimateStsa + (1.f - NS_DD_PR_SNR) * snrLocPost[k];
-      }
-    }
-
-    NS_STAMP(7)
-    // ---- ComputeSpectralFlatness (ns_core.c:523-556)
-    float fd0 = SC_F(S_FD0), fd4 = SC_F(S_FD4), fd6 = SC_F(S_FD6);
-    // (its exponential is evaluated beside bin 128's of exp(-logLrt), each on a lane of one call, once logLrt is
-    // updated: the feature is finished there, in front of its first readers, the histogram and the tanh)
-    float flatArg, flatDen;
-    {
-      float num = flatNum;
-      float den = sumMagn - lane_bcast(magn[0], 0);
-      den = DIV129(den);
-      num = DIV129(num);
-      flatArg = num;
-      flatDen = den;
-    }
-    // ---- ComputeSpectralDifference (ns_core.c:595-634)
-    {
-      float avgMagn = sumMagn;
-      avgPauseMean = DIV129(avgPauseMean);
-      avgMagn = DIV129(avgMagn);
-      float cv[NS3], vp[NS3], vm[NS3];
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) {
-        const float dm = magn[k] - avgMagn, dp = avgPause[k] - avgPauseMean;
-        cv[k] = dm * dp;
-        vp[k] = dp * dp;
-        vm[k] = dm * dm;
-      }
-      float covMagnPause = cv[0] + cv[1], varPause = vp[0] + vp[1], varMagn = vm[0] + vm[1];
-      wave_sums_bcast(covMagnPause, varPause, varMagn);
-      covMagnPause += cv[2];
-      varPause += vp[2];
-      varMagn += vm[2];
-      covMagnPause = DIV129(covMagnPause);
-      varPause = DIV129(varPause);
-      varMagn = DIV129(varMagn);
-      fd6 += signalEnergy;
-      float avgDiffNormMagn = varMagn - fdiv(covMagnPause * covMagnPause, varPause + 0.0001f);
-      avgDiffNormMagn = fdiv(avgDiffNormMagn, fd5 + 0.0001f);
-      fd4 += NS_SPECT_DIFF_TAVG * (avgDiffNormMagn - fd4);
-    }
-
-    NS_STAMP(8)
-    // ---- SpeechNoiseProb (ns_core.c:642-749): the likelihood-ratio update
-    {
-      float t1[NS3], lt1[NS3];
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) t1[k] = 1.f + 2.f * snrLocPrior[k];
-      log_f32_via_tab_n<NS3>(t1, lt1, logts);
-      float tn[NS3], td3[NS3], t2v[NS3];
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) {
-        tn[k] = 2.f * snrLocPrior[k];
-        td3[k] = t1[k] + 0.0001f;
-      }
-      fdiv3(tn, td3, t2v);
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) {
-        const float t2 = t2v[k];
-        const float besselTmp = (snrLocPost[k] + 1.f) * t2;
-        logLrt[k] += NS_LRT_TAVG * (besselTmp - lt1[k] - logLrt[k]);
-      }
-    }
-    float logLrtTimeAvgKsum = SUM3(logLrt);
-    logLrtTimeAvgKsum = DIV129(logLrtTimeAvgKsum);
-    // exp(-logLrt) of the lane's two bins, and two independent wave-uniform exponentials in the third slot of the
-    // same call: the flatness feature's on lane 0, bin 128's on every other lane (read back from lane 1)
-    float ev[NS3];
-    {
-      float nl[NS3];
-#pragma unroll
-      for (int k = 0; k < NS3; ++k) nl[k] = -logLrt[k];
-      nl[2] = lane == 0 ? flatArg : nl[2];
-      exp_f32_via_f64_n<NS3>(nl, ev, exp2s);
-      const float spectralTmp = fdiv(lane_bcast(ev[2], 0), flatDen);  // ns_core.c:551-555
-      fd0 += NS_SPECT_FL_TAVG * (spectralTmp - fd0);
-      ev[2] = lane_bcast(ev[2], 1);
-    }
-
-    NS_STAMP(9)
-    // ---- histograms / prior model (FeatureUpdate, ns_core.c:766-790): the new flatness and difference features, the
-    // previous frame's average LRT
-    float fd3 = SC_F(S_FD3);  // previous frame's average LRT feeds the histogram
-    PriorModel pm;
-    pm.p0 = SC_F(S_PMP0);
-    pm.p1 = SC_F(S_PMP1);
-    pm.p3 = SC_F(S_PMP3);
-    pm.p4 = SC_F(S_PMP4);
-    pm.p5 = SC_F(S_PMP5);
-    pm.p6 = SC_F(S_PMP6);
-    const float pmp2 = SC_F(S_PMP2);
-    int mup0 = updateParsFlag, mup3 = SC_I(S_MUP3);
-    const int mup1 = SC_I(S_MUP1);
-    NS_STEADY(mup3 > 2);
-    bool window_closed = false;
-    if (updateParsFlag >= 1) {
-      mup3--;
-      if (mup3 > 0) {
-        // FeatureParameterExtraction(self, 0), ns_core.c:309-334: lanes 0..2 take one histogram each
-        // (LRT, spectral flatness, spectral difference); one writer per bin and stream, so a
-        // no-return atomic add is the increment without the load -> add -> store round trip
-        const int lane_c = ns_cold(lane);
-        const float fv = lane_c == 0 ? fd3 : (lane_c == 1 ? fd0 : fd4);
-        const float bw = lane_c == 1 ? 0.05f : 0.1f, rbw = lane_c == 1 ? 1.0f / 0.05f : 1.0f / 0.1f;
-        const float lim = lane_c == 1 ? kHist * 0.05f : kHist * 0.1f;
-        if (lane_c < 3 && (fv < lim) && (fv >= 0.0f))
-          atomicAdd(&hist[lane_c * kHistStride + (int)div_by_uniform(fv, bw, rbw)], 1);  // agent scope (sc1)
-      }
-      if (mup3 == 0) {
-        // hand-off build: the no-return increments of the walk's earlier steps are complete before the window is
-        // read, and its clearing stores before the next step's increment
-        if constexpr (FLOW) handoff_drain();
-        pm = close_histogram_window<FLOW>(hist, lane, mup1, mup0 >= 1, pm);
-        if constexpr (FLOW) handoff_drain();
-        window_closed = true;
-        mup3 = mup1;
-        if (updateParsFlag == 1) {
-          mup0 = 0;
-        } else {
-          fd6 = fd6 / ((float)mup1);
-          fd5 = 0.5f * (fd6 + fd5);
-          fd6 = 0.f;
-        }
-      }
-    }
-    fd3 = logLrtTimeAvgKsum;
-    {
-      const float widthPrior0 = NS_WIDTH_PR_MAP, widthPrior1 = 2.f * NS_WIDTH_PR_MAP,
-                  widthPrior2 = 2.f * NS_WIDTH_PR_MAP;
-      const int sgnMap = (int)pmp2;
-      float widthPrior = widthPrior0;
-      if (logLrtTimeAvgKsum < pm.p0) widthPrior = widthPrior1;
-      const float arg0 = widthPrior * (logLrtTimeAvgKsum - pm.p0);
-      widthPrior = widthPrior0;
-      if (sgnMap == 1 && (fd0 > pm.p1)) widthPrior = widthPrior1;
-      if (sgnMap == -1 && (fd0 < pm.p1)) widthPrior = widthPrior1;
-      const float arg1 = (float)sgnMap * widthPrior * (pm.p1 - fd0);
-      widthPrior = widthPrior0;
-      if (fd4 < pm.p3) widthPrior = widthPrior2;
-      const float arg2 = widthPrior * (fd4 - pm.p3);
-      // the three tanh() of :696-725 evaluated on lanes 0..2 of one call
-      const float arg = lane == 0 ? arg0 : (lane == 1 ? arg1 : arg2);
-      const float th = tanh_f32_via_f64(arg, exp2s);
-      const float indicator0 = 0.5f * (lane_bcast(th, 0) + 1.f);
-      const float indicator1 = 0.5f * (lane_bcast(th, 1) + 1.f);
-      const float indicator2 = 0.5f * (lane_bcast(th, 2) + 1.f);
-      const float indPrior = pm.p4 * indicator0 + pm.p5 * indicator1 + pm.p6 * indicator2;
-      priorSpeechProb += NS_PRIOR_UPDATE * (indPrior - priorSpeechProb);
-      if (priorSpeechProb > 1.f) priorSpeechProb = 1.f;
-      if (priorSpeechProb < 0.01f) priorSpeechProb = 0.01f;
-    }
-    float probSpeech[NS3];
-    {
-      const float gainPrior = fdiv(1.f - priorSpeechProb, priorSpeechProb + 0.0001f);
+      NS_STAMP(4)
+      // ---- NoiseEstimation (ns_core.c:217-285)
+      if (updates < NS_END_STARTUP_LONG) updates++;
+      bool quant_new = false;
+      // Bin 128 of the three trackers: three independent chains with one formula, evaluated ONCE with tracker s on
+      // lane 48 + s -- where its lquantile tail already sits in the scalar row; its density tail, three lanes up in
+      // the same DPP row, comes down by one row shift, and n - 1 / n / 1 / n are built per lane from the three
+      // counters.  Every value goes through the operations of its own wave-uniform pass; the other lanes compute
+      // on whatever the row holds and are dropped by the masked merge.
+      constexpr int kLqLane = S_TAIL0 + V_LQ0, kDenLane = S_TAIL0 + V_DEN0;
+      static_assert(V_LQ1 == V_LQ0 + 1 && V_LQ2 == V_LQ0 + 2 && V_DEN1 == V_DEN0 + 1 && V_DEN2 == V_DEN0 + 2 &&
+                    kDenLane == kLqLane + 3 && kLqLane / 16 == (kDenLane + 2) / 16,
+                    "the tracker tails: three + three consecutive lanes of one DPP row");
+      float lqT = sv, denT = dpp_move<0x103>(sv);  // row_shl:3: lane L reads lane L + 3
+      float rcnt1v;
       {
-        float pd[NS3];
-        const float ones[NS3] = {1.f, 1.f, 1.f};
+        const int cntb = lanes3_bits<kLqLane>(counter[0], counter[1], counter[2]);
+        const float cntv = (float)cntb, cnt1v = (float)(cntb + 1);
+        rcnt1v = fdiv(1.f, cnt1v);  // == 1.f / cnt1 (cnt1 = 1 .. 201)
+        tracker_step1(lqT, denT, lmagn[2], cntv, cnt1v, rcnt1v);
+      }
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        {
+          const float cnt = (float)counter[s];
+          const float cnt1 = (float)(counter[s] + 1);
+          const float rcnt1 = lane_bcast(rcnt1v, kLqLane + s);
+          f32x2 lq = {LQ[s][0], LQ[s][1]}, den = {DEN[s][0], DEN[s][1]};
+          tracker_step2(lq, den, f32x2{lmagn[0], lmagn[1]}, cnt, cnt1, rcnt1);
+          LQ[s][0] = lq.x; LQ[s][1] = lq.y;
+          DEN[s][0] = den.x; DEN[s][1] = den.y;
+        }
+        if (counter[s] >= NS_END_STARTUP_LONG) {
+          counter[s] = 0;
+          if (updates >= NS_END_STARTUP_LONG) {
+            LQ[s][2] = lane_bcast(lqT, kLqLane + s);  // the publish wants the tail wave-uniform
+            exp_f32_via_f64_n<NS3>(LQ[s], quant, exp2s);
+            quant_new = true;
+          }
+        }
+        counter[s]++;
+      }
+      if (updates < NS_END_STARTUP_LONG) {
+        LQ[2][2] = lane_bcast(lqT, kLqLane + 2);
+        exp_f32_via_f64_n<NS3>(LQ[2], quant, exp2s);
+        quant_new = true;
+      }
+#pragma unroll
+      for (int k = 0; k < NS3; ++k) noise[k] = quant[k];
+#pragma unroll
+      for (int s = 0; s < 3; ++s) sa.st2(kOffVec + (V_LQ0 + s) * kVecStride, 2 * lane, LQ[s][0], LQ[s][1]);
+#pragma unroll
+      for (int s = 0; s < 3; ++s) sa.st2(kOffVec + (V_DEN0 + s) * kVecStride, 2 * lane, DEN[s][0], DEN[s][1]);
+      sv = mergelanes_vgpr<(7ull << kLqLane)>(sv, lqT);
+      sv = mergelanes_vgpr<(7ull << kDenLane)>(sv, dpp_move<0x113>(denT));  // row_shr:3: lane L reads lane L - 3
+      // the published quantile changes once in ~67 frames past start-up (a tracker publishes every 200
+      // frames, ns_core.c:262-270): its row is written back only then (wave-uniform branch)
+      if (quant_new) STORE3(V_QUANT, quant)
+
+      NS_STAMP(5)
+      // ---- startup noise model (ns_core.c:1091-1100, 1109-1162)
+      float whiteNoiseLevel = SC_F(S_WHITE);
+      float pinkNoiseNumerator = SC_F(S_PINKNUM);
+      float pinkNoiseExp = SC_F(S_PINKEXP);
+      float fd5 = SC_F(S_FD5);
+      const bool startup = blockInd < NS_END_STARTUP_SHORT;
+      if (startup) {
+        const int binA_c = ns_cold(binA);
+        const NsTables* Tc = ns_cold(T);
+        float lm3[NS3], lilm[NS3];
 #pragma unroll
         for (int k = 0; k < NS3; ++k) {
-          float invLrt = ev[k];
-          invLrt = (float)gainPrior * invLrt;
-          pd[k] = 1.f + invLrt;
+          const int bin = k < 2 ? binA_c + 32 * k : 128;
+          const float li = Tc->logi[bin];
+          lm3[k] = bin >= NS_START_BAND ? lmagn[k] : 0.f;
+          lilm[k] = bin >= NS_START_BAND ? li * lmagn[k] : 0.f;
         }
-        fdiv3(ones, pd, probSpeech);
+        const float sum_log_magn = SUM3(lm3);
+        const float sum_log_i_log_magn = SUM3(lilm);
+        const float sum_log_i = Tc->sum_log_i, sum_log_i_square = Tc->sum_log_i_square;
+        whiteNoiseLevel += DIV129(sumMagn) * overdrive;
+        float tmpFloat1 = sum_log_i_square * ((float)(kBins - NS_START_BAND));
+        tmpFloat1 -= (sum_log_i * sum_log_i);
+        float tmpFloat2 = (sum_log_i_square * sum_log_magn - sum_log_i * sum_log_i_log_magn);
+        float tmpFloat3 = tmpFloat2 / tmpFloat1;
+        if (tmpFloat3 < 0.f) tmpFloat3 = 0.f;
+        pinkNoiseNumerator += tmpFloat3;
+        tmpFloat2 = (sum_log_i * sum_log_magn);
+        tmpFloat2 -= ((float)(kBins - NS_START_BAND)) * sum_log_i_log_magn;
+        tmpFloat3 = tmpFloat2 / tmpFloat1;
+        if (tmpFloat3 < 0.f) tmpFloat3 = 0.f;
+        if (tmpFloat3 > 1.f) tmpFloat3 = 1.f;
+        pinkNoiseExp += tmpFloat3;
+        float parametric_num = 0.f, parametric_exp = 0.f;
+        if (pinkNoiseExp > 0.f) {
+          parametric_num = (float)exp((double)(pinkNoiseNumerator / (float)(blockInd + 1)));
+          parametric_num *= (float)(blockInd + 1);
+          parametric_exp = pinkNoiseExp / (float)(blockInd + 1);
+        }
+        float pn[NS3];
+#pragma unroll
+        for (int k = 0; k < NS3; ++k) {
+          const int bin = k < 2 ? binA_c + 32 * k : 128;
+          if (pinkNoiseExp == 0.f) {
+            pn[k] = whiteNoiseLevel;
+          } else {
+            const float use_band = (float)(bin < NS_START_BAND ? NS_START_BAND : bin);
+            pn[k] = (float)((double)parametric_num / pow((double)use_band, (double)parametric_exp));
+          }
+          noise[k] *= (blockInd);
+          const float t2 = pn[k] * (NS_END_STARTUP_SHORT - blockInd);
+          noise[k] += (t2 / (float)(blockInd + 1));
+          noise[k] /= NS_END_STARTUP_SHORT;
+        }
+        if constexpr (FLOW) {  // (a cold row: in memory, the lane's offset from the opaque copy)
+          sa.st2(kOffVec + V_PARAMNOISE * kVecStride, 2 * ns_cold(lane), pn[0], pn[1]);
+          SC_SET_F(S_TAIL0 + V_PARAMNOISE, pn[2]);
+        } else {
+          STORE3(V_PARAMNOISE, pn)
+        }
       }
-    }
+      if (blockInd < NS_END_STARTUP_LONG) {  // ns_core.c:1165-1169
+        fd5 *= blockInd;
+        fd5 += signalEnergy;
+        fd5 /= (blockInd + 1);
+      }
 
-    NS_STAMP(10)
-    // ---- UpdateNoiseEstimate (ns_core.c:800-846): the time constant carried into bin i is the one
-    // bin i-1 selected.  For q > 0 bin i-1 is the same slot of lane L - 2; for q == 0 it is bin
-    // 15 + 16 (t - 1) + 64 g (t > 0) or bin 63 (bin 64), i.e. a slot of lane 30 / 31 (+ 32 g):
-    //   slot 0 (t = h):     h = 1: lane 30 + 32 g slot 0;   h = 0, g = 1: lane 31 slot 1;   bin 0: none
-    //   slot 1 (t = h + 2): h = 0: lane 31 + 32 g slot 0;   h = 1: lane 30 + 32 g slot 1
-    {
-      const int srcA = q > 0 ? lane - 2 : (h ? 30 + 32 * g : 31);
-      const int srcB = q > 0 ? lane - 2 : (h ? 30 + 32 * g : 31 + 32 * g);
-      const bool a_from1 = q == 0 && h == 0;  // slot 0 takes the source lane's slot 1
-      const bool b_from1 = q > 0 || h == 1;   // slot 1 takes the source lane's slot 1
-      const float a0 = __shfl(probSpeech[0], srcA, 64), a1 = __shfl(probSpeech[1], srcA, 64);
-      const float b0 = __shfl(probSpeech[0], srcB, 64), b1 = __shfl(probSpeech[1], srcB, 64);
-      float prevProb[NS3];
-      prevProb[0] = a_from1 ? a1 : a0;
-      prevProb[1] = b_from1 ? b1 : b0;
-      prevProb[2] = lane_bcast(probSpeech[1], 63);  // bin 128 <- bin 127 (q = 15, g = 1, t = 3)
-      // ns_core.c:813-845.  The update with a time constant g is u(g) = g noisePrev + (1 - g) x, x = (1 -
-      // ps) magn + ps noisePrev; the reference computes u(gammaOld) and, when gammaNew differs, keeps the
-      // smaller of u(gammaOld) and u(gammaNew).  With both constants' updates at hand that is: the old
-      // bin's choice, the new bin's choice, their minimum (equal choices give the same value twice).
+      NS_STAMP(6)
+      // ---- ComputeSnr (ns_core.c:566-588)
+      float snrLocPost[NS3], snrLocPrior[NS3];
       {
-        const F3 np(noisePrev), mg(magn), ps(probSpeech), ap(avgPause);
-        const F3 x = (1.f - ps) * mg + ps * np;
-        const F3 uS = NS_SPEECH_UPDATE * np + (1.f - NS_SPEECH_UPDATE) * x;
-        const F3 uN = NS_NOISE_UPDATE * np + (1.f - NS_NOISE_UPDATE) * x;
-        B3 oldSpeech = gt3(F3(prevProb), F3(NS_PROB_RANGE));
-        oldSpeech.v[0] = oldSpeech.v[0] && lane != 0;  // bin 0 has no predecessor: gamma = NOISE_UPDATE
-        const F3 uOld = sel3(oldSpeech, uS, uN);
-        const F3 uNew = sel3(gt3(ps, F3(NS_PROB_RANGE)), uS, uN);
-        min3(uOld, uNew).store(noise);
-        sel3(lt3(ps, F3(NS_PROB_RANGE)), ap + NS_GAMMA_PAUSE * (mg - ap), ap).store(avgPause);
+        float dn1[NS3], dn2[NS3], q1[NS3], q2[NS3];
+#pragma unroll
+        for (int k = 0; k < NS3; ++k) {
+          dn1[k] = noisePrev[k] + 0.0001f;
+          dn2[k] = noise[k] + 0.0001f;
+        }
+        fdiv3(magnPrevA, dn1, q1);
+        fdiv3(magn, dn2, q2);  // used where magn > noise
+#pragma unroll
+        for (int k = 0; k < NS3; ++k) {
+          const float previousEstimateStsa = q1[k] * smooth[k];
+          prevStsa[k] = previousEstimateStsa;
+          snrLocPost[k] = 0.f;
+          if (magn[k] > noise[k]) snrLocPost[k] = q2[k] - 1.f;
+          snrLocPrior[k] = NS_DD_PR_SNR * previousEstimateStsa + (1.f - NS_DD_PR_SNR) * snrLocPost[k];
+        }
       }
-    }
-    STORE3(V_LOGLRT, logLrt) STORE3(V_AVGPAUSE, avgPause)
-    STORE3(V_MAGNPREV_A, magn)  // ns_core.c:1180 (== magnPrevProcess while paired)
 
-    NS_STAMP(11)
-    // ---- Process: decision-directed Wiener gain (ns_core.c:985-1007, 1276-1307)
-    float initMagn[NS3], pnoise[NS3];
-    if (startup) {  // ns_core.c:1268-1272
-      if constexpr (FLOW) {
-        // the two cold rows stay in memory and are written and read back inside a walk: the wave's stores to them
-        // (this step's V_PARAMNOISE, the previous step's V_INITMAGN) are complete before it reads
-        handoff_drain();
-        const int lane2_c = 2 * ns_cold(lane);
-        const float2 im_ = sa.ld2(kOffVec + V_INITMAGN * kVecStride, lane2_c);
-        const float2 pn_ = sa.ld2(kOffVec + V_PARAMNOISE * kVecStride, lane2_c);
-        initMagn[0] = im_.x; initMagn[1] = im_.y;
-        pnoise[0] = pn_.x; pnoise[1] = pn_.y;
-        LOADT(initMagn, V_INITMAGN) LOADT(pnoise, V_PARAMNOISE)
-#pragma unroll
-        for (int k = 0; k < NS3; ++k) initMagn[k] += magn[k];
-        sa.st2(kOffVec + V_INITMAGN * kVecStride, lane2_c, initMagn[0], initMagn[1]);
-        SC_SET_F(S_TAIL0 + V_INITMAGN, initMagn[2]);
-      } else {
-        LOAD3(initMagn, V_INITMAGN)
-        LOAD3(pnoise, V_PARAMNOISE)
-#pragma unroll
-        for (int k = 0; k < NS3; ++k) initMagn[k] += magn[k];
-        STORE3(V_INITMAGN, initMagn)
+      NS_STAMP(7)
+      // ---- ComputeSpectralFlatness (ns_core.c:523-556)
+      float fd0 = SC_F(S_FD0), fd4 = SC_F(S_FD4), fd6 = SC_F(S_FD6);
+      // (its exponential is evaluated beside bin 128's of exp(-logLrt), each on a lane of one call, once logLrt is
+      // updated: the feature is finished there, in front of its first readers, the histogram and the tanh)
+      float flatArg, flatDen;
+      {
+        float num = flatNum;
+        float den = sumMagn - lane_bcast(magn[0], 0);
+        den = DIV129(den);
+        num = DIV129(num);
+        flatArg = num;
+        flatDen = den;
       }
-    }
-    float gainv[NS3];
-    float gq1[NS3], gq2[NS3], snrP[NS3];
-    {
-      float gd1[NS3], gd2[NS3];
+      // ---- ComputeSpectralDifference (ns_core.c:595-634)
+      {
+        float avgMagn = sumMagn;
+        avgPauseMean = DIV129(avgPauseMean);
+        avgMagn = DIV129(avgMagn);
+        float cv[NS3], vp[NS3], vm[NS3];
 #pragma unroll
-      for (int k = 0; k < NS3; ++k) gd1[k] = noise[k] + 0.0001f;
-      fdiv3(magn, gd1, gq1);  // used where magn > noise
+        for (int k = 0; k < NS3; ++k) {
+          const float dm = magn[k] - avgMagn, dp = avgPause[k] - avgPauseMean;
+          cv[k] = dm * dp;
+          vp[k] = dp * dp;
+          vm[k] = dm * dm;
+        }
+        float covMagnPause = cv[0] + cv[1], varPause = vp[0] + vp[1], varMagn = vm[0] + vm[1];
+        wave_sums_bcast(covMagnPause, varPause, varMagn);
+        covMagnPause += cv[2];
+        varPause += vp[2];
+        varMagn += vm[2];
+        covMagnPause = DIV129(covMagnPause);
+        varPause = DIV129(varPause);
+        varMagn = DIV129(varMagn);
+        fd6 += signalEnergy;
+        float avgDiffNormMagn = varMagn - fdiv(covMagnPause * covMagnPause, varPause + 0.0001f);
+        avgDiffNormMagn = fdiv(avgDiffNormMagn, fd5 + 0.0001f);
+        fd4 += NS_SPECT_DIFF_TAVG * (avgDiffNormMagn - fd4);
+      }
+
+      NS_STAMP(8)
+      // ---- SpeechNoiseProb (ns_core.c:642-749): the likelihood-ratio update
+      {
+        float t1[NS3], lt1[NS3];
+#pragma unroll
+        for (int k = 0; k < NS3; ++k) t1[k] = 1.f + 2.f * snrLocPrior[k];
+        log_f32_via_tab_n<NS3>(t1, lt1, logts);
+        float tn[NS3], td3[NS3], t2v[NS3];
+#pragma unroll
+        for (int k = 0; k < NS3; ++k) {
+          tn[k] = 2.f * snrLocPrior[k];
+          td3[k] = t1[k] + 0.0001f;
+        }
+        fdiv3(tn, td3, t2v);
+#pragma unroll
+        for (int k = 0; k < NS3; ++k) {
+          const float t2 = t2v[k];
+          const float besselTmp = (snrLocPost[k] + 1.f) * t2;
+          logLrt[k] += NS_LRT_TAVG * (besselTmp - lt1[k] - logLrt[k]);
+        }
+      }
+      float logLrtTimeAvgKsum = SUM3(logLrt);
+      logLrtTimeAvgKsum = DIV129(logLrtTimeAvgKsum);
+      // exp(-logLrt) of the lane's two bins, and two independent wave-uniform exponentials in the third slot of the
+      // same call: the flatness feature's on lane 0, bin 128's on every other lane (read back from lane 1)
+      float ev[NS3];
+      {
+        float nl[NS3];
+#pragma unroll
+        for (int k = 0; k < NS3; ++k) nl[k] = -logLrt[k];
+        nl[2] = lane == 0 ? flatArg : nl[2];
+        exp_f32_via_f64_n<NS3>(nl, ev, exp2s);
+        const float spectralTmp = fdiv(lane_bcast(ev[2], 0), flatDen);  // ns_core.c:551-555
+        fd0 += NS_SPECT_FL_TAVG * (spectralTmp - fd0);
+        ev[2] = lane_bcast(ev[2], 1);
+      }
+
+      NS_STAMP(9)
+      // ---- histograms / prior model (FeatureUpdate, ns_core.c:766-790): the new flatness and difference features, the
+      // previous frame's average LRT
+      float fd3 = SC_F(S_FD3);  // previous frame's average LRT feeds the histogram
+      PriorModel pm;
+      pm.p0 = SC_F(S_PMP0);
+      pm.p1 = SC_F(S_PMP1);
+      pm.p3 = SC_F(S_PMP3);
+      pm.p4 = SC_F(S_PMP4);
+      pm.p5 = SC_F(S_PMP5);
+      pm.p6 = SC_F(S_PMP6);
+      const float pmp2 = SC_F(S_PMP2);
+      int mup0 = updateParsFlag, mup3 = ss.mup3;
+      const int mup1 = SC_I(S_MUP1);
+      bool window_closed = false;
+      if (updateParsFlag >= 1) {
+        mup3--;
+        if (mup3 > 0) {
+          // FeatureParameterExtraction(self, 0), ns_core.c:309-334: lanes 0..2 take one histogram each
+          // (LRT, spectral flatness, spectral difference); one writer per bin and stream, so a
+          // no-return atomic add is the increment without the load -> add -> store round trip
+          const int lane_c = ns_cold(lane);
+          const float fv = lane_c == 0 ? fd3 : (lane_c == 1 ? fd0 : fd4);
+          const float bw = lane_c == 1 ? 0.05f : 0.1f, rbw = lane_c == 1 ? 1.0f / 0.05f : 1.0f / 0.1f;
+          const float lim = lane_c == 1 ? kHist * 0.05f : kHist * 0.1f;
+          if (lane_c < 3 && (fv < lim) && (fv >= 0.0f))
+            atomicAdd(&hist[lane_c * kHistStride + (int)div_by_uniform(fv, bw, rbw)], 1);  // agent scope (sc1)
+        }
+        if (mup3 == 0) {
+          // hand-off build: the no-return increments of the walk's earlier steps are complete before the window is
+          // read, and its clearing stores before the next step's increment
+          if constexpr (FLOW) handoff_drain();
+          pm = close_histogram_window<FLOW>(hist, lane, mup1, mup0 >= 1, pm);
+          if constexpr (FLOW) handoff_drain();
+          window_closed = true;
+          mup3 = mup1;
+          if (updateParsFlag == 1) {
+            mup0 = 0;
+          } else {
+            fd6 = fd6 / ((float)mup1);
+            fd5 = 0.5f * (fd6 + fd5);
+            fd6 = 0.f;
+          }
+        }
+      }
+      fd3 = logLrtTimeAvgKsum;
+      {
+        const float widthPrior0 = NS_WIDTH_PR_MAP, widthPrior1 = 2.f * NS_WIDTH_PR_MAP,
+                    widthPrior2 = 2.f * NS_WIDTH_PR_MAP;
+        const int sgnMap = (int)pmp2;
+        float widthPrior = widthPrior0;
+        if (logLrtTimeAvgKsum < pm.p0) widthPrior = widthPrior1;
+        const float arg0 = widthPrior * (logLrtTimeAvgKsum - pm.p0);
+        widthPrior = widthPrior0;
+        if (sgnMap == 1 && (fd0 > pm.p1)) widthPrior = widthPrior1;
+        if (sgnMap == -1 && (fd0 < pm.p1)) widthPrior = widthPrior1;
+        const float arg1 = (float)sgnMap * widthPrior * (pm.p1 - fd0);
+        widthPrior = widthPrior0;
+        if (fd4 < pm.p3) widthPrior = widthPrior2;
+        const float arg2 = widthPrior * (fd4 - pm.p3);
+        // the three tanh() of :696-725 evaluated on lanes 0..2 of one call
+        const float arg = lane == 0 ? arg0 : (lane == 1 ? arg1 : arg2);
+        const float th = tanh_f32_via_f64(arg, exp2s);
+        const float indicator0 = 0.5f * (lane_bcast(th, 0) + 1.f);
+        const float indicator1 = 0.5f * (lane_bcast(th, 1) + 1.f);
+        const float indicator2 = 0.5f * (lane_bcast(th, 2) + 1.f);
+        const float indPrior = pm.p4 * indicator0 + pm.p5 * indicator1 + pm.p6 * indicator2;
+        priorSpeechProb += NS_PRIOR_UPDATE * (indPrior - priorSpeechProb);
+        if (priorSpeechProb > 1.f) priorSpeechProb = 1.f;
+        if (priorSpeechProb < 0.01f) priorSpeechProb = 0.01f;
+      }
+      float probSpeech[NS3];
+      {
+        const float gainPrior = fdiv(1.f - priorSpeechProb, priorSpeechProb + 0.0001f);
+        {
+          float pd[NS3];
+          const float ones[NS3] = {1.f, 1.f, 1.f};
+#pragma unroll
+          for (int k = 0; k < NS3; ++k) {
+            float invLrt = ev[k];
+            invLrt = (float)gainPrior * invLrt;
+            pd[k] = 1.f + invLrt;
+          }
+          fdiv3(ones, pd, probSpeech);
+        }
+      }
+
+      NS_STAMP(10)
+      // ---- UpdateNoiseEstimate (ns_core.c:800-846): the time constant carried into bin i is the one
+      // bin i-1 selected.  For q > 0 bin i-1 is the same slot of lane L - 2; for q == 0 it is bin
+      // 15 + 16 (t - 1) + 64 g (t > 0) or bin 63 (bin 64), i.e. a slot of lane 30 / 31 (+ 32 g):
+      //   slot 0 (t = h):     h = 1: lane 30 + 32 g slot 0;   h = 0, g = 1: lane 31 slot 1;   bin 0: none
+      //   slot 1 (t = h + 2): h = 0: lane 31 + 32 g slot 0;   h = 1: lane 30 + 32 g slot 1
+      {
+        const int srcA = q > 0 ? lane - 2 : (h ? 30 + 32 * g : 31);
+        const int srcB = q > 0 ? lane - 2 : (h ? 30 + 32 * g : 31 + 32 * g);
+        const bool a_from1 = q == 0 && h == 0;  // slot 0 takes the source lane's slot 1
+        const bool b_from1 = q > 0 || h == 1;   // slot 1 takes the source lane's slot 1
+        const float a0 = __shfl(probSpeech[0], srcA, 64), a1 = __shfl(probSpeech[1], srcA, 64);
+        const float b0 = __shfl(probSpeech[0], srcB, 64), b1 = __shfl(probSpeech[1], srcB, 64);
+        float prevProb[NS3];
+        prevProb[0] = a_from1 ? a1 : a0;
+        prevProb[1] = b_from1 ? b1 : b0;
+        prevProb[2] = lane_bcast(probSpeech[1], 63);  // bin 128 <- bin 127 (q = 15, g = 1, t = 3)
+        // ns_core.c:813-845.  The update with a time constant g is u(g) = g noisePrev + (1 - g) x, x = (1 -
+        // ps) magn + ps noisePrev; the reference computes u(gammaOld) and, when gammaNew differs, keeps the
+        // smaller of u(gammaOld) and u(gammaNew).  With both constants' updates at hand that is: the old
+        // bin's choice, the new bin's choice, their minimum (equal choices give the same value twice).
+        {
+          const F3 np(noisePrev), mg(magn), ps(probSpeech), ap(avgPause);
+          const F3 x = (1.f - ps) * mg + ps * np;
+          const F3 uS = NS_SPEECH_UPDATE * np + (1.f - NS_SPEECH_UPDATE) * x;
+          const F3 uN = NS_NOISE_UPDATE * np + (1.f - NS_NOISE_UPDATE) * x;
+          B3 oldSpeech = gt3(F3(prevProb), F3(NS_PROB_RANGE));
+          oldSpeech.v[0] = oldSpeech.v[0] && lane != 0;  // bin 0 has no predecessor: gamma = NOISE_UPDATE
+          const F3 uOld = sel3(oldSpeech, uS, uN);
+          const F3 uNew = sel3(gt3(ps, F3(NS_PROB_RANGE)), uS, uN);
+          min3(uOld, uNew).store(noise);
+          sel3(lt3(ps, F3(NS_PROB_RANGE)), ap + NS_GAMMA_PAUSE * (mg - ap), ap).store(avgPause);
+        }
+      }
+      STORE3(V_LOGLRT, logLrt) STORE3(V_AVGPAUSE, avgPause)
+      STORE3(V_MAGNPREV_A, magn)  // ns_core.c:1180 (== magnPrevProcess while paired)
+
+      NS_STAMP(11)
+      // ---- Process: decision-directed Wiener gain (ns_core.c:985-1007, 1276-1307)
+      float initMagn[NS3], pnoise[NS3];
+      if (startup) {  // ns_core.c:1268-1272
+        if constexpr (FLOW) {
+          // the two cold rows stay in memory and are written and read back inside a walk: the wave's stores to them
+          // (this step's V_PARAMNOISE, the previous step's V_INITMAGN) are complete before it reads
+          handoff_drain();
+          const int lane2_c = 2 * ns_cold(lane);
+          const float2 im_ = sa.ld2(kOffVec + V_INITMAGN * kVecStride, lane2_c);
+          const float2 pn_ = sa.ld2(kOffVec + V_PARAMNOISE * kVecStride, lane2_c);
+          initMagn[0] = im_.x; initMagn[1] = im_.y;
+          pnoise[0] = pn_.x; pnoise[1] = pn_.y;
+          LOADT(initMagn, V_INITMAGN) LOADT(pnoise, V_PARAMNOISE)
+#pragma unroll
+          for (int k = 0; k < NS3; ++k) initMagn[k] += magn[k];
+          sa.st2(kOffVec + V_INITMAGN * kVecStride, lane2_c, initMagn[0], initMagn[1]);
+          SC_SET_F(S_TAIL0 + V_INITMAGN, initMagn[2]);
+        } else {
+          LOAD3(initMagn, V_INITMAGN)
+          LOAD3(pnoise, V_PARAMNOISE)
+#pragma unroll
+          for (int k = 0; k < NS3; ++k) initMagn[k] += magn[k];
+          STORE3(V_INITMAGN, initMagn)
+        }
+      }
+      float gainv[NS3];
+      float gq1[NS3], gq2[NS3], snrP[NS3];
+      {
+        float gd1[NS3], gd2[NS3];
+#pragma unroll
+        for (int k = 0; k < NS3; ++k) gd1[k] = noise[k] + 0.0001f;
+        fdiv3(magn, gd1, gq1);  // used where magn > noise
+#pragma unroll
+        for (int k = 0; k < NS3; ++k) {
+          float currentEstimateStsa = 0.f;
+          if (magn[k] > noise[k]) currentEstimateStsa = gq1[k] - 1.f;
+          snrP[k] = NS_DD_PR_SNR * prevStsa[k] + (1.f - NS_DD_PR_SNR) * currentEstimateStsa;
+          gd2[k] = overdrive + snrP[k];
+        }
+        fdiv3(snrP, gd2, gq2);
+      }
 #pragma unroll
       for (int k = 0; k < NS3; ++k) {
-        float currentEstimateStsa = 0.f;
-        if (magn[k] > noise[k]) currentEstimateStsa = gq1[k] - 1.f;
-        snrP[k] = NS_DD_PR_SNR * prevStsa[k] + (1.f - NS_DD_PR_SNR) * currentEstimateStsa;
-        gd2[k] = overdrive + snrP[k];
+        float gg = fmin_raw(fmax_raw(gq2[k], denoiseBound), 1.f);  // ns_core.c:1001-1006
+        if (startup) {
+          float tmp = (initMagn[k] - overdrive * pnoise[k]);
+          tmp /= (initMagn[k] + 0.0001f);
+          if (tmp < denoiseBound) tmp = denoiseBound;
+          if (tmp > 1.f) tmp = 1.f;
+          gg *= (blockInd);
+          tmp *= (NS_END_STARTUP_SHORT - blockInd);
+          gg += tmp;
+          gg /= (NS_END_STARTUP_SHORT);
+        }
+        gainv[k] = gg;
+        re[k] *= gg;
+        im[k] *= gg;
       }
-      fdiv3(snrP, gd2, gq2);
-    }
-#pragma unroll
-    for (int k = 0; k < NS3; ++k) {
-      float gg = fmin_raw(fmax_raw(gq2[k], denoiseBound), 1.f);  // ns_core.c:1001-1006
+      STORE3(V_SMOOTH, gainv)      // ns_core.c:1304
+      STORE3(V_NOISEPREV, noise)   // ns_core.c:1310
+
+      NS_STAMP(12)
+      NS_NEXT_FRAME()
+      // ---- IFFT (ns_core.c:923-944)
+      er = f32x2{re[0], re[1]};
+      ei = f32x2{im[0], im[1]};
+      if (lane == 0) ei.x = re[2];  // Ooura packing: a[1] = R128
+      real_split1(tile, spls, lane, er, ei, true);
+      lds_sync1();
+      {
+        const int base = 64 * g + q + 16 * h;
+        float* tf = reinterpret_cast<float*>(tile);
+        tf[2 * base] = er.x;
+        tf[2 * base + 1] = ei.x;
+        tf[2 * base + 64] = er.y;
+        tf[2 * base + 65] = ei.y;
+      }
+      lds_sync1();
+      f32x2 tr, ti;  // samples 2E (tr) and 2E + 1 (ti) of elements E = binA (slot 0) and binA + 32 (slot 1)
+      {
+        f32x2 ea, eb;
+        cft128_passes1(tile, tws, fl, lane, ea, eb);
+        radix2_tail1(ea, eb, gmask, true, tr, ti);
+      }
+      const float td0 = tr.x * (2.f / kAnal), td1 = ti.x * (2.f / kAnal);
+      const float td2 = tr.y * (2.f / kAnal), td3s = ti.y * (2.f / kAnal);
+
+      NS_STAMP(13)
+      // ---- energy-based gain compensation (ns_core.c:1315-1342)
+      float factor = 1.f;
+      if (gainmap == 1 && blockInd > NS_END_STARTUP_LONG) {
+        float factor1 = 1.f, factor2 = 1.f;
+        float e2 = td0 * td0;
+        e2 += td1 * td1;
+        e2 += td2 * td2;
+        e2 += td3s * td3s;
+        const float energy2 = wave_sum_bcast(e2);
+        float gain = fsqrt(fdiv(energy2, energy1 + 1.f));
+        if (gain > NS_B_LIM) {
+          factor1 = 1.f + 1.3f * (gain - NS_B_LIM);
+          if (gain * factor1 > 1.f) factor1 = fdiv(1.f, gain);
+        }
+        if (gain < NS_B_LIM) {
+          if (gain <= denoiseBound) gain = denoiseBound;
+          factor2 = 1.f - 0.3f * (NS_B_LIM - gain);
+        }
+        factor = priorSpeechProb * factor1 + (1.f - priorSpeechProb) * factor2;
+      }
+
+      // ---- synthesis window, overlap-add, emit 160, carry 96 (ns_core.c:1344-1359)
+      {
+        float* y = IO16 ? reinterpret_cast<float*>(reinterpret_cast<short*>(outj) + (size_t)stream * kBlockL)
+                        : outj + (size_t)stream * kBlockL;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const int nA = 2 * ns_cold(binA), nB = nA + 64;  // sample index of td0 / td2
+        const float2 wA = *reinterpret_cast<const float2*>(wins + nA);
+        const float2 wB = *reinterpret_cast<const float2*>(wins + nB);
+        const float cA0 = g == 0 ? carryA.x : 0.f, cA1 = g == 0 ? carryA.y : 0.f;
+        const float cB0 = (g == 0 && h == 0) ? carryB.x : 0.f, cB1 = (g == 0 && h == 0) ? carryB.y : 0.f;
+        const float oA0 = cA0 + factor * (wA.x * td0), oA1 = cA1 + factor * (wA.y * td1);
+        const float oB0 = cB0 + factor * (wB.x * td2), oB1 = cB1 + factor * (wB.y * td3s);
+        if (nA >= 160) {
+          sa.st2(kOffSynt, nA - 160, oA0, oA1);
+        } else {
+          store2p<IO16>(y, nA, sat16p(oA0), sat16p(oA1));
+        }
+        if (nB >= 160) {
+          sa.st2(kOffSynt, nB - 160, oB0, oB1);
+        } else {
+          store2p<IO16>(y, nB, sat16p(oB0), sat16p(oB1));
+        }
+      }
+
+      NS_STAMP(14)
+      // ---- commit scalars
+      SC_SET_I(S_UPDATES, updates);
+      SC_SET_I(S_COUNTER0, counter[0]);
+      SC_SET_I(S_COUNTER1, counter[1]);
+      SC_SET_I(S_COUNTER2, counter[2]);
+      SC_SET_I(S_MUP0, mup0);
+      SC_SET_I(S_MUP3, mup3);
+      SC_SET_F(S_SIGNALENERGY, signalEnergy);
+      SC_SET_F(S_SUMMAGN, sumMagn);
       if (startup) {
-        float tmp = (initMagn[k] - overdrive * pnoise[k]);
-        tmp /= (initMagn[k] + 0.0001f);
-        if (tmp < denoiseBound) tmp = denoiseBound;
-        if (tmp > 1.f) tmp = 1.f;
-        gg *= (blockInd);
-        tmp *= (NS_END_STARTUP_SHORT - blockInd);
-        gg += tmp;
-        gg /= (NS_END_STARTUP_SHORT);
+        SC_SET_F(S_WHITE, whiteNoiseLevel);
+        SC_SET_F(S_PINKNUM, pinkNoiseNumerator);
+        SC_SET_F(S_PINKEXP, pinkNoiseExp);
       }
-      gainv[k] = gg;
-      re[k] *= gg;
-      im[k] *= gg;
-    }
-    STORE3(V_SMOOTH, gainv)      // ns_core.c:1304
-    STORE3(V_NOISEPREV, noise)   // ns_core.c:1310
-
-    NS_STAMP(12)
-    NS_NEXT_FRAME()
-    // ---- IFFT (ns_core.c:923-944)
-    er = f32x2{re[0], re[1]};
-    ei = f32x2{im[0], im[1]};
-    if (lane == 0) ei.x = re[2];  // Ooura packing: a[1] = R128
-    real_split1(tile, spls, lane, er, ei, true);
-    lds_sync1();
-    {
-      const int base = 64 * g + q + 16 * h;
-      float* tf = reinterpret_cast<float*>(tile);
-      tf[2 * base] = er.x;
-      tf[2 * base + 1] = ei.x;
-      tf[2 * base + 64] = er.y;
-      tf[2 * base + 65] = ei.y;
-    }
-    lds_sync1();
-    f32x2 tr, ti;  // samples 2E (tr) and 2E + 1 (ti) of elements E = binA (slot 0) and binA + 32 (slot 1)
-    {
-      f32x2 ea, eb;
-      cft128_passes1(tile, tws, fl, lane, ea, eb);
-      radix2_tail1(ea, eb, gmask, true, tr, ti);
-    }
-    const float td0 = tr.x * (2.f / kAnal), td1 = ti.x * (2.f / kAnal);
-    const float td2 = tr.y * (2.f / kAnal), td3s = ti.y * (2.f / kAnal);
-
-    NS_STAMP(13)
-    // ---- energy-based gain compensation (ns_core.c:1315-1342)
-    float factor = 1.f;
-    if (gainmap == 1 && blockInd > NS_END_STARTUP_LONG) {
-      float factor1 = 1.f, factor2 = 1.f;
-      float e2 = td0 * td0;
-      e2 += td1 * td1;
-      e2 += td2 * td2;
-      e2 += td3s * td3s;
-      const float energy2 = wave_sum_bcast(e2);
-      float gain = fsqrt(fdiv(energy2, energy1 + 1.f));
-      if (gain > NS_B_LIM) {
-        factor1 = 1.f + 1.3f * (gain - NS_B_LIM);
-        if (gain * factor1 > 1.f) factor1 = fdiv(1.f, gain);
+      if (window_closed) {
+        SC_SET_F(S_PMP0, pm.p0);
+        SC_SET_F(S_PMP1, pm.p1);
+        SC_SET_F(S_PMP3, pm.p3);
+        SC_SET_F(S_PMP4, pm.p4);
+        SC_SET_F(S_PMP5, pm.p5);
+        SC_SET_F(S_PMP6, pm.p6);
       }
-      if (gain < NS_B_LIM) {
-        if (gain <= denoiseBound) gain = denoiseBound;
-        factor2 = 1.f - 0.3f * (NS_B_LIM - gain);
-      }
-      factor = priorSpeechProb * factor1 + (1.f - priorSpeechProb) * factor2;
-    }
-
-    // ---- synthesis window, overlap-add, emit 160, carry 96 (ns_core.c:1344-1359)
-    {
-      float* y = IO16 ? reinterpret_cast<float*>(reinterpret_cast<short*>(outj) + (size_t)stream * kBlockL)
-                      : outj + (size_t)stream * kBlockL;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      const int nA = 2 * ns_cold(binA), nB = nA + 64;  // sample index of td0 / td2
-      const float2 wA = *reinterpret_cast<const float2*>(wins + nA);
-      const float2 wB = *reinterpret_cast<const float2*>(wins + nB);
-      const float cA0 = g == 0 ? carryA.x : 0.f, cA1 = g == 0 ? carryA.y : 0.f;
-      const float cB0 = (g == 0 && h == 0) ? carryB.x : 0.f, cB1 = (g == 0 && h == 0) ? carryB.y : 0.f;
-      const float oA0 = cA0 + factor * (wA.x * td0), oA1 = cA1 + factor * (wA.y * td1);
-      const float oB0 = cB0 + factor * (wB.x * td2), oB1 = cB1 + factor * (wB.y * td3s);
-      if (nA >= 160) {
-        sa.st2(kOffSynt, nA - 160, oA0, oA1);
-      } else {
-        store2p<IO16>(y, nA, sat16p(oA0), sat16p(oA1));
-      }
-      if (nB >= 160) {
-        sa.st2(kOffSynt, nB - 160, oB0, oB1);
-      } else {
-        store2p<IO16>(y, nB, sat16p(oB0), sat16p(oB1));
-      }
-    }
-
-    NS_STAMP(14)
-    // ---- commit scalars
-    SC_SET_I(S_UPDATES, updates);
-    SC_SET_I(S_COUNTER0, counter[0]);
-    SC_SET_I(S_COUNTER1, counter[1]);
-    SC_SET_I(S_COUNTER2, counter[2]);
-    SC_SET_I(S_MUP0, mup0);
-    SC_SET_I(S_MUP3, mup3);
-    SC_SET_F(S_SIGNALENERGY, signalEnergy);
-    SC_SET_F(S_SUMMAGN, sumMagn);
-    if (startup) {
-      SC_SET_F(S_WHITE, whiteNoiseLevel);
-      SC_SET_F(S_PINKNUM, pinkNoiseNumerator);
-      SC_SET_F(S_PINKEXP, pinkNoiseExp);
-    }
-    if (window_closed) {
-      SC_SET_F(S_PMP0, pm.p0);
-      SC_SET_F(S_PMP1, pm.p1);
-      SC_SET_F(S_PMP3, pm.p3);
-      SC_SET_F(S_PMP4, pm.p4);
-      SC_SET_F(S_PMP5, pm.p5);
-      SC_SET_F(S_PMP6, pm.p6);
-    }
-    SC_SET_F(S_FD0, fd0);
-    SC_SET_F(S_FD3, fd3);
-    SC_SET_F(S_FD4, fd4);
-    SC_SET_F(S_FD5, fd5);
-    SC_SET_F(S_FD6, fd6);
-    SC_SET_I(S_BLOCKIND, blockInd);
-    SC_SET_F(S_PRIORSPEECHPROB, priorSpeechProb);
+      SC_SET_F(S_FD0, fd0);
+      SC_SET_F(S_FD3, fd3);
+      SC_SET_F(S_FD4, fd4);
+      SC_SET_F(S_FD5, fd5);
+      SC_SET_F(S_FD6, fd6);
+      SC_SET_I(S_BLOCKIND, blockInd);
+      SC_SET_F(S_PRIORSPEECHPROB, priorSpeechProb);
+    };  // step_rest
+    if (__builtin_expect(step_steady, 1)) step_rest(std::true_type{});
+    else step_rest(std::false_type{});
     if constexpr (!FLOW) sa.st1(kOffScalars, lane, sv);  // (hand-off build: with the image, at the walk's end)
     NS_STAMP(15)
-    NS_STREAM_DONE()
+    NS_STREAM_DONE(0)
   }
 #undef NS_STREAM_DONE
 #undef NS_NEXT_FRAME
 #undef NS_STAMP
+#undef NS_BUDGET_ASIDE
+#undef NS_BUDGET_BACK
 #undef SC_I
 #undef SC_F
 #undef SC_SET_I
@@ -1060,21 +1170,50 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
 #undef SUM3
 }
 
+// the product kernels: the four DIAG = false instantiations
+template <bool IO16, bool FLOW>
+__global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ state,
+                                                           int32_t* __restrict__ hist_all,
+                                                           const NsTables* __restrict__ T,
+                                                           const float* __restrict__ in,
+                                                           float* __restrict__ out,
+                                                           int num_streams, int steady_on, NsFlowArgs fa) {
+  ns_frame1_run<IO16, FLOW, false>(state, hist_all, T, in, out, num_streams, steady_on, fa, NsDiagArgs{nullptr, 0});
+}
+
+// the diagnostic kernels (stamps, timeline, step counts): float frames only, which is what their entry points use
+template <bool FLOW>
+__global__ __launch_bounds__(256, 4) void ns_frame1_diag_kernel(float* __restrict__ state,
+                                                                int32_t* __restrict__ hist_all,
+                                                                const NsTables* __restrict__ T,
+                                                                const float* __restrict__ in,
+                                                                float* __restrict__ out,
+                                                                int num_streams, int steady_on, NsFlowArgs fa,
+                                                                NsDiagArgs dg) {
+  ns_frame1_run<false, FLOW, true>(state, hist_all, T, in, out, num_streams, steady_on, fa, dg);
+}
+
 }  // namespace
 
 namespace aspns {
 
+// stamps / step_counts: diagnostics; either one selects the diagnostic kernel (float frames only)
 hipError_t launch_ns_frame1(bool io16, float* state, int32_t* hist, const NsTables* T,
-                            const float* in, float* out, int num_streams, hipStream_t s,
-                            unsigned long long* stamps, int stamp_mode) {
+                            const float* in, float* out, int num_streams, hipStream_t s, int steady_on,
+                            unsigned long long* stamps, int stamp_mode, unsigned* step_counts) {
   const dim3 grid((num_streams + 3) / 4), block(256);
   const NsFlowArgs none = {{nullptr, nullptr}, 0u, 0, 1, 0u, 1u, 1u};
-  if (io16)
+  if (stamps != nullptr || step_counts != nullptr) {
+    if (io16) return hipErrorInvalidValue;
+    const NsDiagArgs dg = {stamps != nullptr ? (void*)stamps : (void*)step_counts, stamps != nullptr ? (stamp_mode != 0 ? 1 : 0) : 2};
+    hipLaunchKernelGGL((ns_frame1_diag_kernel<false>), grid, block, 0, s, state, hist, T, in, out, num_streams,
+                       steady_on, none, dg);
+  } else if (io16)
     hipLaunchKernelGGL((ns_frame1_kernel<true, false>), grid, block, 0, s, state, hist, T, in, out,
-                       num_streams, stamps, stamp_mode, none);
+                       num_streams, steady_on, none);
   else
     hipLaunchKernelGGL((ns_frame1_kernel<false, false>), grid, block, 0, s, state, hist, T, in, out,
-                       num_streams, stamps, stamp_mode, none);
+                       num_streams, steady_on, none);
   return hipGetLastError();
 }
 
@@ -1085,17 +1224,23 @@ hipError_t launch_ns_frame1(bool io16, float* state, int32_t* hist, const NsTabl
 hipError_t launch_ns_frame1_flow(bool io16, float* state, int32_t* hist, const NsTables* T,
                                  const float* in, float* out, int num_streams, hipStream_t s,
                                  unsigned* seq, unsigned* abort_w, unsigned want, int steps, int walk, int slot0,
-                                 int ring, size_t per, unsigned long long* stamps) {
+                                 int ring, size_t per, int steady_on, unsigned long long* stamps,
+                                 unsigned* step_counts) {
   walk = walk < 1 ? 1 : (walk > steps ? steps : walk);
   const int gx = ((num_streams + 3) / 4 + 7) / 8 * 8;
   const dim3 grid(gx, (steps + walk - 1) / walk), block(256);
   const NsFlowArgs fa = {{seq, abort_w}, want, slot0, ring, (unsigned)per, (unsigned)steps, (unsigned)walk};
-  if (io16)
+  if (stamps != nullptr || step_counts != nullptr) {
+    if (io16) return hipErrorInvalidValue;
+    const NsDiagArgs dg = {stamps != nullptr ? (void*)stamps : (void*)step_counts, stamps != nullptr ? 0 : 2};
+    hipLaunchKernelGGL((ns_frame1_diag_kernel<true>), grid, block, 0, s, state, hist, T, in, out, num_streams,
+                       steady_on, fa, dg);
+  } else if (io16)
     hipLaunchKernelGGL((ns_frame1_kernel<true, true>), grid, block, 0, s, state, hist, T, in, out,
-                       num_streams, stamps, 0, fa);
+                       num_streams, steady_on, fa);
   else
     hipLaunchKernelGGL((ns_frame1_kernel<false, true>), grid, block, 0, s, state, hist, T, in, out,
-                       num_streams, stamps, 0, fa);
+                       num_streams, steady_on, fa);
   return hipGetLastError();
 }
 

@@ -72,6 +72,8 @@ def load_library():
         "AspNsBatch_SetSplit": [vp, ip],
         "AspNsBatch_SetFlow": [vp, ip],
         "AspNsBatch_SetFlowWalk": [vp, ip],
+        "AspNsBatch_SetSteady": [vp, ip],
+        "AspNsBatch_DebugStepCounts": [vp, ip, vp],
         "AspNsBatch_DebugFlowChunks": [vp, C.POINTER(C.c_int)],
         "AspNsBatch_DebugFlowDesync": [vp],
         "AspNsBatch_SetKernel": [vp, ip],
@@ -293,6 +295,17 @@ class NsBatch:
     def set_flow_walk(self, steps):
         """Hand-off build: frame steps of a launch one workgroup walks; 0 auto, 1..64 forced (include/asp_ns.h)."""
         _check(self.lib.AspNsBatch_SetFlowWalk(self.h, steps), "AspNsBatch_SetFlowWalk")
+
+    def set_steady(self, on):
+        """Steady-state body of the frame step: -1 default (on; ASP_NS_STEADY=0 off), 0 off, 1 on (include/asp_ns.h)."""
+        _check(self.lib.AspNsBatch_SetSteady(self.h, on), "AspNsBatch_SetSteady")
+
+    def debug_step_counts(self, on=True):
+        """Test hook: [num_streams][2] frame steps that took the steady / the generic body since it was switched on."""
+        counts = np.zeros((self.S, 2), dtype=np.uint32)
+        _check(self.lib.AspNsBatch_DebugStepCounts(self.h, 1 if on else 0, C.c_void_p(counts.ctypes.data)),
+               "AspNsBatch_DebugStepCounts")
+        return counts
 
     def set_split(self, parts):
         _check(self.lib.AspNsBatch_SetSplit(self.h, parts), "AspNsBatch_SetSplit")

@@ -205,6 +205,18 @@ int AspNsBatch_SetFlow(AspNsBatch* b, int mode);
  * that boundary: the comment above flow_walk_auto in csrc/ns_api.hip).  1..64 force a length (the environment variable
  * ASP_NS_FLOW_WALK does the same for batches left on auto).  Same results bit for bit for every value. */
 int AspNsBatch_SetFlowWalk(AspNsBatch* b, int steps);
+/* Pair-layout kernel: a frame step of a stream in steady state -- past both start-up windows, no quantile tracker
+ * publishing, the feature-histogram window staying open, gain compensation on: all but a few steps in 200 of a
+ * long-running stream -- takes a body compiled under those conditions, every other step the generic one; one
+ * wave-uniform predicate chooses per step.  Same arithmetic, same results bit for bit.  on: -1 = default (on; the
+ * environment variable ASP_NS_STEADY=0 turns the default off), 0 = off (every step through the generic body: A / B
+ * runs and tests), 1 = on. */
+int AspNsBatch_SetSteady(AspNsBatch* b, int on);
+/* Test hook: on != 0 makes the batch's pair-layout launches (float frames) run the diagnostic kernels, which add up,
+ * per stream, the frame steps that took the steady body and the generic one; counts ([num_streams][2], host, may be
+ * NULL) receives the sums so far.  on == 0 reads them a last time and returns to the product kernels.  While it is on,
+ * an int16 call (AnalyzeProcessS16) is refused with ASP_ERR_STATE: the diagnostic kernels take float frames. */
+int AspNsBatch_DebugStepCounts(AspNsBatch* b, int on, unsigned* counts);
 /* Test hook: the grid's y extent (chunks of steps = ceil(steps / walk)) of the batch's last hand-off launch of the
  * pair-layout kernel; 0 before the first one. */
 int AspNsBatch_DebugFlowChunks(AspNsBatch* b, int* chunks);

@@ -1,16 +1,29 @@
 #!/usr/bin/env python3
 """Per-phase instruction budget of the fused NS frame kernels (costs no GPU time).
 
-Compiles the kernel source with -DNS1_BUDGET (ns_kernels1.hip): the NS_STAMP marks become assembly
-comments and the steady-state conditions (past start-up, no tracker publish, histogram window open,
-no libm fallback) are asserted, so the code between two marks is what one wave executes per frame.
-Prints, per phase, the instruction classes of the <IO16 = false> instantiation; branch targets that
-survive are listed so that a cold block cannot hide inside a phase.
+Compiles the kernel source with -DNS1_BUDGET (ns_kernels1.hip): the PRODUCT code -- both bodies of the step, the
+run-time predicate between them, no assumption beyond the product's own -- with the NS_STAMP marks as assembly comments
+and nothing else changed (no scheduling barrier at a mark: the scheduler may move an instruction across one, so the
+per-phase rows are approximate and only their sum is exact).  A mark names the body it stands in: 0 the shared code
+(head of the step up to the predicate, tail behind the two bodies), 1 the steady body, 2 the generic body, 3 aside:
+blocks the source brackets as not part of a step that goes on (NS_BUDGET_ASIDE .. NS_BUDGET_BACK in ns_kernels1.hip:
+the zero-energy exit with its copy of the next step's head, the walk's write-back, drain and publish, the copy of the
+head in front of the loop).
+Prints, per body and phase, the instruction classes of the <IO16 = false> instantiation in layout order; branch
+targets are counted per row so that a conditional block cannot hide inside a phase.
 
 --flow selects the hand-off instantiation <IO16 = false, FLOW = true> (the headline of bench.py) instead of the first
 <false, ...> match (the plain build), compiles with the per-file flags of build.py (EXTRA["ns_kernels1.hip"]: the
-register figures of that instantiation depend on them) and adds a "loop body" row: what lies between the header of
-the step loop and its back edge, i.e. one steady-state frame step without the once-per-chunk set-up in front of it.
+register figures of that instantiation depend on them) and adds two rows.  "steady step": the sum of the shared rows
+(-) and the steady body's rows (S): what a wave executes in a step of the steady body that is followed by another
+step of its walk.  The aside rows (A) are left out.  How the conditional blocks that remain in it are counted: in
+full, as if entered every step -- the libm fallbacks the compiler left inline and the per-lane branches ("branch
+targets inside" counts them); the row is an upper bound of the executed path by those blocks only.  Attribution is by
+layout order (an instruction belongs to the last mark in front of it), so a block the compiler moved behind another
+mark is counted there.  "generic body": the instructions under the generic body's marks, for comparison.
+The marks are asm volatile statements: they keep the compiler from moving memory operations across them, so the
+marked build is scheduled a little differently from the product (the hand-off instantiation: 126 VGPRs against 116;
+the register figures printed at the end are the marked build's, profiles/*_resource_usage.txt has the product's).
 
 usage: tools/ns_valu_budget.py [source.hip] [--flow] [--dump out.s] [extra hipcc flags...]
 """
@@ -116,62 +129,60 @@ def main():
         body.append(l)
         if l.strip().startswith(".Lfunc_end"):
             break
-    phase = -1
+    phase = (0, -1)
     per = collections.OrderedDict()
     labels = collections.defaultdict(list)
-    # the step loop (--flow): the backward branch with the longest reach that spans phase marks, and its target
-    loop = None
-    if flow:
-        where = {}
-        for n, l in enumerate(body):
-            m = re.match(r"^(\.LBB\S+):", l.strip())
-            if m:
-                where[m.group(1)] = n
-        marks = [n for n, l in enumerate(body) if l.strip().startswith("; NS_PHASE")]
-        for n, l in enumerate(body):
-            t = l.split()
-            if len(t) >= 2 and t[0].startswith(("s_cbranch", "s_branch")) and where.get(t[1], n) < n:
-                h = where[t[1]]
-                if any(h < k < n for k in marks) and (loop is None or n - h > loop[1] - loop[0]):
-                    loop = (h, n)
     inloop = collections.Counter()
+    inloop_labels = 0
+    generic = collections.Counter()
     for n, l in enumerate(body):
         t = l.strip()
-        m = re.match(r"; NS_PHASE (\d+)", t)
+        m = re.match(r"; NS_PHASE (\d+) body (\d)", t)
         if m:
-            phase = int(m.group(1))
+            phase = (int(m.group(2)), int(m.group(1)))
             continue
         if not t or t.startswith((";", ".")) and not re.match(r"^\.LBB", t):
             continue
         if re.match(r"^\.LBB\S+:", t):
             labels[phase].append(t.split(":")[0])
+            if phase[1] >= 0 and phase[0] in (0, 1):
+                inloop_labels += 1
             continue
         op = t.split()[0]
         per.setdefault(phase, collections.Counter())[classify(op)] += 1
-        if loop and loop[0] <= n <= loop[1]:
+        if phase[1] >= 0 and phase[0] in (0, 1):
             inloop[classify(op)] += 1
+        if phase[0] == 2:
+            generic[classify(op)] += 1
     cols = list(VALU) + ["s_nop", "salu", "lds", "vmem", "waitcnt", "branch"]
     print("%-18s %5s %6s | " % ("phase", "VALU", "cycles") + " ".join("%7s" % c for c in cols))
     tot = collections.Counter()
     for ph, c in per.items():
         v = sum(c[k] for k in VALU)
-        name = "prologue" if ph < 0 else "%2d %s" % (ph, NAMES[ph] if ph < len(NAMES) else "")
+        name = "prologue" if ph[1] < 0 else "%s%2d %s" % ("-SGA"[ph[0]], ph[1], NAMES[ph[1]] if ph[1] < len(NAMES) else "aside")
         cyc = sum(c[k] * PRICE[k] for k in VALU)
         print("%-18s %5d %6.0f | " % (name, v, cyc) + " ".join("%7d" % c[k] for k in cols) + ("   labels: %d" % len(labels[ph]) if labels[ph] else ""))
         tot.update(c)
     v = sum(tot[k] for k in VALU)
     print("%-18s %5d %6.0f | " % ("total", v, sum(tot[k] * PRICE[k] for k in VALU)) + " ".join("%7d" % tot[k] for k in cols))
     if flow:
-        if loop:
+        if inloop:
             v = sum(inloop[k] for k in VALU)
-            print("%-18s %5d %6.0f | " % ("loop body", v, sum(inloop[k] * PRICE[k] for k in VALU)) + " ".join("%7d" % inloop[k] for k in cols)
-                  + "   (%s .. its back edge)" % body[loop[0]].strip().rstrip(":"))
+            print("%-18s %5d %6.0f | " % ("steady step", v, sum(inloop[k] * PRICE[k] for k in VALU)) + " ".join("%7d" % inloop[k] for k in cols)
+                  + "   (rows - and S; branch targets inside: %d)" % inloop_labels)
+            v = sum(generic[k] for k in VALU)
+            print("%-18s %5d %6.0f | " % ("generic body", v, sum(generic[k] * PRICE[k] for k in VALU)) + " ".join("%7d" % generic[k] for k in cols))
         else:
-            print("loop body: no backward branch across the phase marks found")
-    m = re.search(r"\.vgpr_count:\s+(\d+)", "\n".join(lines[::-1]))
+            print("steady step: no phase marks found")
+    # register figures of every kernel of the (marked) build, by name
+    name = None
     for l in lines:
-        if "vgpr_count" in l or "sgpr_count" in l or "vgpr_spill" in l:
-            print(l.strip())
+        m = re.match(r"\s*\.name:\s+(\S+)", l)
+        if m and not m.group(1).endswith(".kd"):
+            name = m.group(1)
+        m = re.match(r"\s*\.(sgpr_count|vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\d+)", l)
+        if m:
+            print("%-22s %4s  %s" % (m.group(1), m.group(2), name))
 
 
 if __name__ == "__main__":

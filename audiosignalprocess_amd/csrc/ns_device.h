@@ -1,14 +1,12 @@
-// ns_device.h -- device-side helpers shared by the NS kernels (ns_kernels.hip: one stream per
-// wave, bins q / q + 64; ns_kernels1.hip: one stream per wave, pair layout): the reference's constants, exact division /
-// sqrt / log / exp / tanh forms (each verified exhaustively against its libm form on the device,
-// tests/test_ns_gpu.py), wave reductions, and the histogram-window close.
+// ns_device.h -- device-side arithmetic that is not specific to the noise suppressor (the NS kernels and
+// aec_kernels.hip include it): wave and DPP operations, exact division forms, packed three- and five-bin
+// vectors, and the lean fp64 sqrt / log / exp / tanh / pow / sincos (each verified exhaustively against its libm
+// form on the device, tests/test_ns_gpu.py, tests/test_aec_gpu.py).  The NS step's own text -- the reference's
+// constants, its wave-uniform scalar sections, the histogram-window close -- is in ns_step.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "ns_layout.h"
-
 namespace aspns_dev {
-using namespace aspns;
 
 // instruction-budget builds (tools/ns_valu_budget.py, never shipped) assert that the rarely taken
 // libm fallbacks are not taken, so that they vanish from the straight-line code being counted
@@ -17,25 +15,6 @@ using namespace aspns;
 #else
 #define ASP_NS_RARE(c) __builtin_expect((c), 0)
 #endif
-
-// ns/defines.h:19-48, same (float)<double literal> spelling as the reference
-#define NS_QUANTILE (float)0.25
-#define NS_END_STARTUP_LONG 200
-#define NS_END_STARTUP_SHORT 50
-#define NS_FACTOR (float)40.0
-#define NS_WIDTH (float)0.01
-#define NS_DD_PR_SNR (float)0.98
-#define NS_LRT_TAVG (float)0.50
-#define NS_SPECT_FL_TAVG (float)0.30
-#define NS_SPECT_DIFF_TAVG (float)0.30
-#define NS_PRIOR_UPDATE (float)0.10
-#define NS_NOISE_UPDATE (float)0.90
-#define NS_SPEECH_UPDATE (float)0.99
-#define NS_WIDTH_PR_MAP (float)4.0
-#define NS_PROB_RANGE (float)0.20
-#define NS_GAMMA_PAUSE (float)0.05
-#define NS_B_LIM (float)0.5
-#define NS_START_BAND 5
 
 __device__ __forceinline__ float xorf(float x, uint32_t m) {
   return __uint_as_float(__float_as_uint(x) ^ m);
@@ -242,35 +221,6 @@ __device__ __forceinline__ void fdiv3(const float (&n)[3], const float (&d)[3], 
   q[0] = a.x; q[1] = a.y;
   q[2] = fdiv(n[2], d[2]);
 }
-// One step of a quantile tracker (ns_core.c:232-260) in the branch-free form of the frame kernels: delta = FACTOR /
-// max(density, 1) (the quotient by 1 is exact), the step carries its sign -- lq += (+QUANTILE delta) / n or (-(1 -
-// QUANTILE) delta) / n (products, quotients and x + (-y) are sign-symmetric) -- and the density moves where the new
-// lq lies within WIDTH of the log magnitude.  cnt = n - 1, cnt1 = n, rcnt1 = 1 / n (rounded) as floats.
-// The packed form serves a lane's two owned bins of ONE tracker (cnt, cnt1, rcnt1 wave-uniform); the scalar form
-// serves bin 128 of the three trackers at once, tracker s on its own lane with its own cnt / cnt1 / rcnt1: the same
-// IEEE operations on the same operands in the same order as three wave-uniform passes.
-__device__ __forceinline__ void tracker_step2(f32x2& lq, f32x2& den, f32x2 lm, float cnt, float cnt1, float rcnt1) {
-  const f32x2 dm = {fmax_raw(den.x, 1.0f), fmax_raw(den.y, 1.0f)};
-  const float fac = NS_FACTOR * 1.f, qp = NS_QUANTILE, qm = -(1.f - NS_QUANTILE), wd = NS_WIDTH;
-  const f32x2 delta = fdiv2(f32x2{fac, fac}, dm);
-  const f32x2 coef = {lm.x > lq.x ? qp : qm, lm.y > lq.y ? qp : qm};
-  const f32x2 rd = {rcnt1, rcnt1}, nd1 = {-cnt1, -cnt1};
-  {
-    const f32x2 a = coef * delta, q0 = a * rd;
-    lq = lq + __builtin_elementwise_fma(__builtin_elementwise_fma(nd1, q0, a), rd, q0);
-  }
-  const f32x2 a = f32x2{cnt, cnt} * den + f32x2{1.f / (2.f * wd), 1.f / (2.f * wd)}, q0 = a * rd;
-  const f32x2 nd = __builtin_elementwise_fma(__builtin_elementwise_fma(nd1, q0, a), rd, q0);
-  den = f32x2{fabsf(lm.x - lq.x) < wd ? nd.x : den.x, fabsf(lm.y - lq.y) < wd ? nd.y : den.y};
-}
-__device__ __forceinline__ void tracker_step1(float& lq, float& den, float lm, float cnt, float cnt1, float rcnt1) {
-  const float fac = NS_FACTOR * 1.f, qp = NS_QUANTILE, qm = -(1.f - NS_QUANTILE), wd = NS_WIDTH;
-  const float delta = fdiv(fac, fmax_raw(den, 1.0f));
-  const float coef = lm > lq ? qp : qm;
-  lq = lq + div_by_uniform(coef * delta, cnt1, rcnt1);
-  const float nd = div_by_uniform(cnt * den + 1.f / (2.f * wd), cnt1, rcnt1);
-  den = fabsf(lm - lq) < wd ? nd : den;
-}
 // ---- the two-streams-per-wave kernel (ns_kernels2.hip): four owned bins + bin 128 per lane
 __device__ __forceinline__ void fdiv5(const float (&n)[5], const float (&d)[5], float (&q)[5]) {
   const f32x2 a = fdiv2(f32x2{n[0], n[1]}, f32x2{d[0], d[1]});
@@ -335,7 +285,6 @@ __device__ __forceinline__ F5 div_by_uniform5(const F5& a, float d, float rd) {
 __device__ __forceinline__ F5 fdiv5v(const F5& n, const F5& d) {
   return F5(fdiv2(n.a, d.a), fdiv2(n.b, d.b), fdiv(n.t, d.t));
 }
-#define DIV129(a) div_by_uniform((a), 129.0f, 1.0f / 129.0f)
 
 // (float)log((double)x), the reference's idiom (ns_core.c:228,540,681,1096), for
 // positive finite normal x.  Lean fp64 evaluation:
@@ -656,136 +605,5 @@ __device__ __forceinline__ void sincos_f32_via_f64(float x, float& s_out, float&
     c_out = (float)cos((double)x);
   }
 }
-
-// --------------------------------------------------------------------------
-// Histogram window close: FeatureParameterExtraction(self, 1), ns_core.c:337-517.
-// Runs once per 500 frames per stream.  Zero bins cannot change any of the
-// running sums / peaks, so only non-empty bins are visited, in bin order, which
-// keeps the reference's sequential float sums and tie-breaking exactly.
-struct PriorModel {
-  float p0, p1, p3, p4, p5, p6;
-};
-
-// FLOW (ns_kernels1.hip's hand-off build): the histogram is read and cleared with agent-scope (sc1)
-// accesses, like every other state access of that build.
-template <bool FLOW>
-__device__ __forceinline__ int hist_ld(const int32_t* p) {
-  typedef __attribute__((address_space(1))) int gi32;
-  if constexpr (FLOW) return __hip_atomic_load((const gi32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else return *p;
-}
-template <bool FLOW>
-__device__ __forceinline__ void hist_st(int32_t* p, int v) {
-  typedef __attribute__((address_space(1))) int gi32;
-  if constexpr (FLOW) __hip_atomic_store((gi32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *p = v;
-}
-
-template <bool FLOW = false>
-__device__ inline __attribute__((noinline)) PriorModel close_histogram_window(int32_t* __restrict__ hist, int lane,
-                                                          int updateWindow, bool zero_after,
-                                                          PriorModel pm) {
-  // ---- LRT histogram, :340-373
-  float avgHistLrt = 0.f, avgHistLrtCompl = 0.f, avgSquareHistLrt = 0.f;
-  int numHistLrt = 0;
-  for (int r = 0; r < 16; ++r) {
-    const int i = r * 64 + lane;
-    const int v = i < kHist ? hist_ld<FLOW>(hist + i) : 0;
-    unsigned long long m = __ballot(v != 0);
-    while (m) {
-      const int p = __ffsll((long long)m) - 1;
-      m &= m - 1;
-      const int hv = __shfl(v, p, 64);
-      const float binMid = ((float)(r * 64 + p) + 0.5f) * 0.1f;
-      if (binMid <= 1.f) {
-        avgHistLrt += hv * binMid;
-        numHistLrt += hv;
-      }
-      avgSquareHistLrt += hv * binMid * binMid;
-      avgHistLrtCompl += hv * binMid;
-    }
-  }
-  if (numHistLrt > 0) avgHistLrt = avgHistLrt / ((float)numHistLrt);
-  avgHistLrtCompl = avgHistLrtCompl / ((float)updateWindow);
-  avgSquareHistLrt = avgSquareHistLrt / ((float)updateWindow);
-  const float fluctLrt = avgSquareHistLrt - avgHistLrt * avgHistLrtCompl;
-  if (fluctLrt < 0.05f) {
-    pm.p0 = 1.f;
-  } else {
-    pm.p0 = 1.2f * avgHistLrt;
-    if (pm.p0 < 0.2f) pm.p0 = 0.2f;
-    if (pm.p0 > 1.f) pm.p0 = 1.f;
-  }
-  // ---- two dominant peaks of the flatness and difference histograms, :378-432
-  float pos1[2], pos2[2];
-  int wt1[2], wt2[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int32_t* hh = hist + (k + 1) * kHistStride;
-    const float binSize = k == 0 ? 0.05f : 0.1f;
-    int maxPeak1 = 0, maxPeak2 = 0;
-    pos1[k] = 0.f;
-    pos2[k] = 0.f;
-    wt1[k] = 0;
-    wt2[k] = 0;
-    for (int r = 0; r < 16; ++r) {
-      const int i = r * 64 + lane;
-      const int v = i < kHist ? hist_ld<FLOW>(hh + i) : 0;
-      unsigned long long m = __ballot(v != 0);
-      while (m) {
-        const int p = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const int hv = __shfl(v, p, 64);
-        const float binMid = ((float)(r * 64 + p) + 0.5f) * binSize;
-        if (hv > maxPeak1) {
-          maxPeak2 = maxPeak1;
-          wt2[k] = wt1[k];
-          pos2[k] = pos1[k];
-          maxPeak1 = hv;
-          wt1[k] = hv;
-          pos1[k] = binMid;
-        } else if (hv > maxPeak2) {
-          maxPeak2 = hv;
-          wt2[k] = hv;
-          pos2[k] = binMid;
-        }
-      }
-    }
-  }
-  const int thresWeight = (int)(0.3 * updateWindow);  // :67-70
-  // ---- flatness, :435-463
-  int useFlat = 1;
-  if ((fabsf(pos2[0] - pos1[0]) < 2 * 0.05f) && (wt2[0] > 0.5f * wt1[0])) {
-    wt1[0] += wt2[0];
-    pos1[0] = 0.5f * (pos1[0] + pos2[0]);
-  }
-  if (wt1[0] < thresWeight || pos1[0] < 0.6f) useFlat = 0;
-  if (useFlat == 1) {
-    pm.p1 = 0.9f * pos1[0];
-    if (pm.p1 < 0.1f) pm.p1 = 0.1f;
-    if (pm.p1 > 0.95f) pm.p1 = 0.95f;
-  }
-  // ---- template difference, :467-498
-  int useDiff = 1;
-  if ((fabsf(pos2[1] - pos1[1]) < 2 * 0.1f) && (wt2[1] > 0.5f * wt1[1])) {
-    wt1[1] += wt2[1];
-    pos1[1] = 0.5f * (pos1[1] + pos2[1]);
-  }
-  pm.p3 = 1.2f * pos1[1];
-  if (wt1[1] < thresWeight) useDiff = 0;
-  if (pm.p3 < 0.16f) pm.p3 = 0.16f;
-  if (pm.p3 > 1.f) pm.p3 = 1.f;
-  if (fluctLrt < 0.05f) useDiff = 0;
-  const float featureSum = (float)(1 + useFlat + useDiff);  // :504-507
-  pm.p4 = 1.f / featureSum;
-  pm.p5 = ((float)useFlat) / featureSum;
-  pm.p6 = ((float)useDiff) / featureSum;
-  if (zero_after) {  // :510-516
-    for (int k = 0; k < 3; ++k)
-      for (int r = 0; r < 16; ++r) hist_st<FLOW>(hist + k * kHistStride + r * 64 + lane, 0);
-  }
-  return pm;
-}
-
 
 }  // namespace aspns_dev

@@ -24,11 +24,17 @@
 // Cross-bin sums use a fixed association (slot-local, then xor 1,2,4,8,16,32)
 // that oracle/ns_oracle.c reproduces in ASP_NS_REDUCE_TREE mode.
 //
+// Of the step's wave-uniform scalar sections, which ns_step.h states once for the three frame kernels, this file calls
+// the start-up average, the flatness feature and the gain factor.  The pink-noise fit, the difference feature's tail,
+// the feature-window bookkeeping and the prior-model update stay written out here: called as functions, each moves the
+// Analyze-only 8 kHz kernel from 86 to 88 VGPRs (tools/listing_diff.py).
+//
 // Compile with -ffp-contract=off: parity depends on unfused mul/add.
 #include <hip/hip_runtime.h>
 
 #include "ns_device.h"
 #include "ns_layout.h"
+#include "ns_step.h"
 
 using namespace aspns;
 
@@ -321,7 +327,7 @@ __global__ __launch_bounds__(256, 4) void ns_frame_kernel(float* __restrict__ st
   constexpr int AN = G8 ? 128 : kAnal;       // analysis window
   constexpr int NB = AN / 2 + 1;             // bins
   // x / NB, correctly rounded (DIV129's form for either bin count)
-#define DIVB(a) div_by_uniform((a), (float)NB, 1.0f / (float)NB)
+#define DIVB(a) ns_div_bins<NB>(a)
   // the lane's partial of a cross-bin sum: its q slot, plus its q + 64 slot where that exists
 #define P2(a0, a1) (G8 ? (a0) : (a0) + (a1))
 
@@ -596,11 +602,7 @@ __global__ __launch_bounds__(256, 4) void ns_frame_kernel(float* __restrict__ st
       }
       STORE_ROW(V_PARAMNOISE, pn)
     }
-    if (blockInd < NS_END_STARTUP_LONG) {  // ns_core.c:1165-1169
-      fd5 *= blockInd;
-      fd5 += signalEnergy;
-      fd5 /= (blockInd + 1);
-    }
+    fd5 = ns_startup_fd5(fd5, signalEnergy, blockInd);
 
     // ---- ComputeSnr (ns_core.c:566-588)
     float snrLocPost[3], snrLocPrior[3];
@@ -623,12 +625,8 @@ __global__ __launch_bounds__(256, 4) void ns_frame_kernel(float* __restrict__ st
       t_ap = t_ap + avgPause[2];
     }
     {
-      float num = wave_sum(t_fl);
-      float den = sumMagn - lane_bcast(magn[0], 0);
-      den = DIVB(den);
-      num = DIVB(num);
-      const float spectralTmp = fdiv(exp_f32_via_f64(num, T->exp2_64), den);
-      fd0 += NS_SPECT_FL_TAVG * (spectralTmp - fd0);
+      const NsFlatArgs flat = ns_flatness_args<NB>(wave_sum(t_fl), sumMagn, lane_bcast(magn[0], 0));
+      fd0 = ns_flatness_update(fd0, exp_f32_via_f64(flat.arg, T->exp2_64), flat.den);
     }
     // ---- ComputeSpectralDifference (ns_core.c:595-634)
     {
@@ -884,24 +882,13 @@ __global__ __launch_bounds__(256, 4) void ns_frame_kernel(float* __restrict__ st
     // ---- energy-based gain compensation (ns_core.c:1315-1342)
     float factor = 1.f;
     if (gainmap == 1 && blockInd > NS_END_STARTUP_LONG) {
-      float factor1 = 1.f, factor2 = 1.f;
       float e2 = td0 * td0;
       e2 += td1 * td1;
       if (!G8) {
         e2 += td2 * td2;
         e2 += td3 * td3;
       }
-      const float energy2 = wave_sum(e2);
-      float gain = fsqrt(fdiv(energy2, energy1 + 1.f));
-      if (gain > NS_B_LIM) {
-        factor1 = 1.f + 1.3f * (gain - NS_B_LIM);
-        if (gain * factor1 > 1.f) factor1 = fdiv(1.f, gain);
-      }
-      if (gain < NS_B_LIM) {
-        if (gain <= denoiseBound) gain = denoiseBound;
-        factor2 = 1.f - 0.3f * (NS_B_LIM - gain);
-      }
-      factor = priorSpeechProb * factor1 + (1.f - priorSpeechProb) * factor2;
+      factor = ns_gain_factor(wave_sum(e2), energy1, denoiseBound, priorSpeechProb);
     }
 
     // ---- synthesis window, overlap-add, emit 160, carry 96 (ns_core.c:1344-1359)

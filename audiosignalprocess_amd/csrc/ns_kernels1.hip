@@ -3,7 +3,7 @@
 //
 // Same arithmetic as ns_frame_kernel<true,true> (ns_kernels.hip) -- every per-bin float operation of
 // ns_core.c:1043-1359 in the reference's order, Ooura-order FFT (fft4g.c), exact libm forms
-// (ns_device.h) -- mapped so that a frame step of 4096 streams is 4096 short waves, all resident at
+// (ns_device.h), the wave-uniform scalar sections of ns_step.h -- mapped so that a frame step of 4096 streams is 4096 short waves, all resident at
 // once (four per SIMD at <= 128 VGPRs): a step is bound by the time a wave needs from its first load
 // to its last store plus the launch boundary (profiles/README.md, rounds 2 and 3).
 //
@@ -31,6 +31,7 @@
 #include "ns_device.h"
 #include "ns_layout.h"
 #include "ns_pair_fft.h"
+#include "ns_step.h"
 
 namespace {
 using namespace asphandoff;
@@ -711,20 +712,11 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         }
         const float sum_log_magn = SUM3(lm3);
         const float sum_log_i_log_magn = SUM3(lilm);
-        const float sum_log_i = Tc->sum_log_i, sum_log_i_square = Tc->sum_log_i_square;
-        whiteNoiseLevel += DIV129(sumMagn) * overdrive;
-        float tmpFloat1 = sum_log_i_square * ((float)(kBins - NS_START_BAND));
-        tmpFloat1 -= (sum_log_i * sum_log_i);
-        float tmpFloat2 = (sum_log_i_square * sum_log_magn - sum_log_i * sum_log_i_log_magn);
-        float tmpFloat3 = tmpFloat2 / tmpFloat1;
-        if (tmpFloat3 < 0.f) tmpFloat3 = 0.f;
-        pinkNoiseNumerator += tmpFloat3;
-        tmpFloat2 = (sum_log_i * sum_log_magn);
-        tmpFloat2 -= ((float)(kBins - NS_START_BAND)) * sum_log_i_log_magn;
-        tmpFloat3 = tmpFloat2 / tmpFloat1;
-        if (tmpFloat3 < 0.f) tmpFloat3 = 0.f;
-        if (tmpFloat3 > 1.f) tmpFloat3 = 1.f;
-        pinkNoiseExp += tmpFloat3;
+        const NsPinkFit fit = ns_pink_fit<kBins>(Tc, whiteNoiseLevel, pinkNoiseNumerator, pinkNoiseExp, sumMagn,
+                                                 overdrive, sum_log_magn, sum_log_i_log_magn, blockInd);
+        whiteNoiseLevel = fit.whiteNoiseLevel;
+        pinkNoiseNumerator = fit.pinkNoiseNumerator;
+        pinkNoiseExp = fit.pinkNoiseExp;
         float parametric_num = 0.f, parametric_exp = 0.f;
         if (pinkNoiseExp > 0.f) {
           parametric_num = (float)exp((double)(pinkNoiseNumerator / (float)(blockInd + 1)));
@@ -753,11 +745,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
           STORE3(V_PARAMNOISE, pn)
         }
       }
-      if (blockInd < NS_END_STARTUP_LONG) {  // ns_core.c:1165-1169
-        fd5 *= blockInd;
-        fd5 += signalEnergy;
-        fd5 /= (blockInd + 1);
-      }
+      fd5 = ns_startup_fd5(fd5, signalEnergy, blockInd);
 
       NS_STAMP(6)
       // ---- ComputeSnr (ns_core.c:566-588)
@@ -786,15 +774,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       float fd0 = SC_F(S_FD0), fd4 = SC_F(S_FD4), fd6 = SC_F(S_FD6);
       // (its exponential is evaluated beside bin 128's of exp(-logLrt), each on a lane of one call, once logLrt is
       // updated: the feature is finished there, in front of its first readers, the histogram and the tanh)
-      float flatArg, flatDen;
-      {
-        float num = flatNum;
-        float den = sumMagn - lane_bcast(magn[0], 0);
-        den = DIV129(den);
-        num = DIV129(num);
-        flatArg = num;
-        flatDen = den;
-      }
+      const NsFlatArgs flat = ns_flatness_args<kBins>(flatNum, sumMagn, lane_bcast(magn[0], 0));
       // ---- ComputeSpectralDifference (ns_core.c:595-634)
       {
         float avgMagn = sumMagn;
@@ -817,9 +797,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         varPause = DIV129(varPause);
         varMagn = DIV129(varMagn);
         fd6 += signalEnergy;
-        float avgDiffNormMagn = varMagn - fdiv(covMagnPause * covMagnPause, varPause + 0.0001f);
-        avgDiffNormMagn = fdiv(avgDiffNormMagn, fd5 + 0.0001f);
-        fd4 += NS_SPECT_DIFF_TAVG * (avgDiffNormMagn - fd4);
+        fd4 = ns_spectral_diff(covMagnPause, varPause, varMagn, fd4, fd5);
       }
 
       NS_STAMP(8)
@@ -852,10 +830,9 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         float nl[NS3];
 #pragma unroll
         for (int k = 0; k < NS3; ++k) nl[k] = -logLrt[k];
-        nl[2] = lane == 0 ? flatArg : nl[2];
+        nl[2] = lane == 0 ? flat.arg : nl[2];
         exp_f32_via_f64_n<NS3>(nl, ev, exp2s);
-        const float spectralTmp = fdiv(lane_bcast(ev[2], 0), flatDen);  // ns_core.c:551-555
-        fd0 += NS_SPECT_FL_TAVG * (spectralTmp - fd0);
+        fd0 = ns_flatness_update(fd0, lane_bcast(ev[2], 0), flat.den);  // ns_core.c:551-555
         ev[2] = lane_bcast(ev[2], 1);
       }
 
@@ -894,14 +871,11 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
           pm = close_histogram_window<FLOW>(hist, lane, mup1, mup0 >= 1, pm);
           if constexpr (FLOW) handoff_drain();
           window_closed = true;
-          mup3 = mup1;
-          if (updateParsFlag == 1) {
-            mup0 = 0;
-          } else {
-            fd6 = fd6 / ((float)mup1);
-            fd5 = 0.5f * (fd6 + fd5);
-            fd6 = 0.f;
-          }
+          const NsWindowOpen wo = ns_window_reopen(updateParsFlag, mup1, fd5, fd6);
+          mup0 = wo.mup0;
+          mup3 = wo.mup3;
+          fd5 = wo.fd5;
+          fd6 = wo.fd6;
         }
       }
       fd3 = logLrtTimeAvgKsum;
@@ -922,13 +896,8 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         // the three tanh() of :696-725 evaluated on lanes 0..2 of one call
         const float arg = lane == 0 ? arg0 : (lane == 1 ? arg1 : arg2);
         const float th = tanh_f32_via_f64(arg, exp2s);
-        const float indicator0 = 0.5f * (lane_bcast(th, 0) + 1.f);
-        const float indicator1 = 0.5f * (lane_bcast(th, 1) + 1.f);
-        const float indicator2 = 0.5f * (lane_bcast(th, 2) + 1.f);
-        const float indPrior = pm.p4 * indicator0 + pm.p5 * indicator1 + pm.p6 * indicator2;
-        priorSpeechProb += NS_PRIOR_UPDATE * (indPrior - priorSpeechProb);
-        if (priorSpeechProb > 1.f) priorSpeechProb = 1.f;
-        if (priorSpeechProb < 0.01f) priorSpeechProb = 0.01f;
+        priorSpeechProb = ns_prior_update(priorSpeechProb, pm, ns_prior_indicator(lane_bcast(th, 0)),
+                                          ns_prior_indicator(lane_bcast(th, 1)), ns_prior_indicator(lane_bcast(th, 2)));
       }
       float probSpeech[NS3];
       {
@@ -1075,22 +1044,11 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       // ---- energy-based gain compensation (ns_core.c:1315-1342)
       float factor = 1.f;
       if (gainmap == 1 && blockInd > NS_END_STARTUP_LONG) {
-        float factor1 = 1.f, factor2 = 1.f;
         float e2 = td0 * td0;
         e2 += td1 * td1;
         e2 += td2 * td2;
         e2 += td3s * td3s;
-        const float energy2 = wave_sum_bcast(e2);
-        float gain = fsqrt(fdiv(energy2, energy1 + 1.f));
-        if (gain > NS_B_LIM) {
-          factor1 = 1.f + 1.3f * (gain - NS_B_LIM);
-          if (gain * factor1 > 1.f) factor1 = fdiv(1.f, gain);
-        }
-        if (gain < NS_B_LIM) {
-          if (gain <= denoiseBound) gain = denoiseBound;
-          factor2 = 1.f - 0.3f * (NS_B_LIM - gain);
-        }
-        factor = priorSpeechProb * factor1 + (1.f - priorSpeechProb) * factor2;
+        factor = ns_gain_factor(wave_sum_bcast(e2), energy1, denoiseBound, priorSpeechProb);
       }
 
       // ---- synthesis window, overlap-add, emit 160, carry 96 (ns_core.c:1344-1359)

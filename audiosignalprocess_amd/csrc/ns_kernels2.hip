@@ -1,8 +1,8 @@
 // ns_kernels2.hip -- the fused Analyze+Process frame step with TWO streams per wave64.
 //
 // Same arithmetic as ns_frame_kernel<true,true> (ns_kernels.hip) -- every per-bin float
-// operation of ns_core.c:1043-1359 in the reference's order, Ooura-order FFT, exact libm forms
-// -- re-mapped for instruction issue, which is what bounds the one-stream-per-wave kernel
+// operation of ns_core.c:1043-1359 in the reference's order, Ooura-order FFT, exact libm forms,
+// the wave-uniform scalar sections of ns_step.h -- re-mapped for instruction issue, which is what bounds the one-stream-per-wave kernel
 // (profiles/README.md: ~4 cycles per wave64 VALU instruction, no cross-wave overlap):
 //
 //   * lanes 0-31 carry stream 2w, lanes 32-63 stream 2w+1; a lane owns 4 bins
@@ -26,6 +26,7 @@
 #include "handoff.h"
 #include "ns_device.h"
 #include "ns_layout.h"
+#include "ns_step.h"
 
 namespace {
 using namespace asphandoff;
@@ -556,20 +557,11 @@ __global__ __launch_bounds__(256, 3) void ns_frame2_kernel(float* __restrict__ s
     }
     const float sum_log_magn = SUM5(lm5);
     const float sum_log_i_log_magn = SUM5(lilm);
-    const float sum_log_i = T->sum_log_i, sum_log_i_square = T->sum_log_i_square;
-    whiteNoiseLevel += DIV129(sumMagn) * overdrive;
-    float tmpFloat1 = sum_log_i_square * ((float)(kBins - NS_START_BAND));
-    tmpFloat1 -= (sum_log_i * sum_log_i);
-    float tmpFloat2 = (sum_log_i_square * sum_log_magn - sum_log_i * sum_log_i_log_magn);
-    float tmpFloat3 = tmpFloat2 / tmpFloat1;
-    if (tmpFloat3 < 0.f) tmpFloat3 = 0.f;
-    pinkNoiseNumerator += tmpFloat3;
-    tmpFloat2 = (sum_log_i * sum_log_magn);
-    tmpFloat2 -= ((float)(kBins - NS_START_BAND)) * sum_log_i_log_magn;
-    tmpFloat3 = tmpFloat2 / tmpFloat1;
-    if (tmpFloat3 < 0.f) tmpFloat3 = 0.f;
-    if (tmpFloat3 > 1.f) tmpFloat3 = 1.f;
-    pinkNoiseExp += tmpFloat3;
+    const NsPinkFit fit = ns_pink_fit<kBins>(T, whiteNoiseLevel, pinkNoiseNumerator, pinkNoiseExp, sumMagn, overdrive,
+                                             sum_log_magn, sum_log_i_log_magn, blockInd);
+    whiteNoiseLevel = fit.whiteNoiseLevel;
+    pinkNoiseNumerator = fit.pinkNoiseNumerator;
+    pinkNoiseExp = fit.pinkNoiseExp;
     float parametric_num = 0.f, parametric_exp = 0.f;
     if (pinkNoiseExp > 0.f) {
       parametric_num = (float)exp((double)(pinkNoiseNumerator / (float)(blockInd + 1)));
@@ -593,11 +585,7 @@ __global__ __launch_bounds__(256, 3) void ns_frame2_kernel(float* __restrict__ s
     }
     STORE5(V_PARAMNOISE, pn)
   }
-  if (blockInd < NS_END_STARTUP_LONG) {  // ns_core.c:1165-1169
-    fd5 *= blockInd;
-    fd5 += signalEnergy;
-    fd5 /= (blockInd + 1);
-  }
+  fd5 = ns_startup_fd5(fd5, signalEnergy, blockInd);
 
   NS_STAMP(6)
   // ---- ComputeSnr (ns_core.c:566-588)
@@ -628,12 +616,8 @@ __global__ __launch_bounds__(256, 3) void ns_frame2_kernel(float* __restrict__ s
     float fl5[NS5];
 #pragma unroll
     for (int k = 0; k < NS5; ++k) fl5[k] = (k == 0 && lam == 0) ? 0.f : lmagn[k];
-    float num = SUM5(fl5);
-    float den = sumMagn - half_lane(magn[0], hb, 0);
-    den = DIV129(den);
-    num = DIV129(num);
-    const float spectralTmp = fdiv(exp_f32_via_f64(num, exp2s), den);
-    fd0 += NS_SPECT_FL_TAVG * (spectralTmp - fd0);
+    const NsFlatArgs flat = ns_flatness_args<kBins>(SUM5(fl5), sumMagn, half_lane(magn[0], hb, 0));
+    fd0 = ns_flatness_update(fd0, exp_f32_via_f64(flat.arg, exp2s), flat.den);
   }
   // ---- ComputeSpectralDifference (ns_core.c:595-634)
   {
@@ -656,9 +640,7 @@ __global__ __launch_bounds__(256, 3) void ns_frame2_kernel(float* __restrict__ s
     varPause = DIV129(varPause);
     varMagn = DIV129(varMagn);
     fd6 += signalEnergy;
-    float avgDiffNormMagn = varMagn - fdiv(covMagnPause * covMagnPause, varPause + 0.0001f);
-    avgDiffNormMagn = fdiv(avgDiffNormMagn, fd5 + 0.0001f);
-    fd4 += NS_SPECT_DIFF_TAVG * (avgDiffNormMagn - fd4);
+    fd4 = ns_spectral_diff(covMagnPause, varPause, varMagn, fd4, fd5);
   }
 
   NS_STAMP(8)
@@ -710,14 +692,11 @@ __global__ __launch_bounds__(256, 3) void ns_frame2_kernel(float* __restrict__ s
     }
     if (updateParsFlag >= 1 && mup3 == 0) {
       window_closed = true;
-      mup3 = mup1;
-      if (updateParsFlag == 1) {
-        mup0 = 0;
-      } else {
-        fd6 = fd6 / ((float)mup1);
-        fd5 = 0.5f * (fd6 + fd5);
-        fd6 = 0.f;
-      }
+      const NsWindowOpen wo = ns_window_reopen(updateParsFlag, mup1, fd5, fd6);
+      mup0 = wo.mup0;
+      mup3 = wo.mup3;
+      fd5 = wo.fd5;
+      fd6 = wo.fd6;
     }
   }
 
@@ -762,13 +741,8 @@ __global__ __launch_bounds__(256, 3) void ns_frame2_kernel(float* __restrict__ s
     // the three tanh() of :696-725 on lanes 0..2 of each half: one call serves both streams
     const float arg = lam == 0 ? arg0 : (lam == 1 ? arg1 : arg2);
     const float th = tanh_f32_via_f64(arg, exp2s);
-    const float indicator0 = 0.5f * (half_lane(th, hb, 0) + 1.f);
-    const float indicator1 = 0.5f * (half_lane(th, hb, 1) + 1.f);
-    const float indicator2 = 0.5f * (half_lane(th, hb, 2) + 1.f);
-    const float indPrior = pm.p4 * indicator0 + pm.p5 * indicator1 + pm.p6 * indicator2;
-    priorSpeechProb += NS_PRIOR_UPDATE * (indPrior - priorSpeechProb);
-    if (priorSpeechProb > 1.f) priorSpeechProb = 1.f;
-    if (priorSpeechProb < 0.01f) priorSpeechProb = 0.01f;
+    priorSpeechProb = ns_prior_update(priorSpeechProb, pm, ns_prior_indicator(half_lane(th, hb, 0)),
+                                      ns_prior_indicator(half_lane(th, hb, 1)), ns_prior_indicator(half_lane(th, hb, 2)));
   }
   float probSpeech[NS5];
   {
@@ -902,21 +876,10 @@ __global__ __launch_bounds__(256, 3) void ns_frame2_kernel(float* __restrict__ s
   // ---- energy-based gain compensation (ns_core.c:1315-1342)
   float factor = 1.f;
   if (gainmap == 1 && blockInd > NS_END_STARTUP_LONG) {
-    float factor1 = 1.f, factor2 = 1.f;
     float e2 = td[0] * td[0];
 #pragma unroll
     for (int k = 1; k < 8; ++k) e2 += td[k] * td[k];
-    const float energy2 = half_sum(e2);
-    float gain = fsqrt(fdiv(energy2, energy1 + 1.f));
-    if (gain > NS_B_LIM) {
-      factor1 = 1.f + 1.3f * (gain - NS_B_LIM);
-      if (gain * factor1 > 1.f) factor1 = fdiv(1.f, gain);
-    }
-    if (gain < NS_B_LIM) {
-      if (gain <= denoiseBound) gain = denoiseBound;
-      factor2 = 1.f - 0.3f * (NS_B_LIM - gain);
-    }
-    factor = priorSpeechProb * factor1 + (1.f - priorSpeechProb) * factor2;
+    factor = ns_gain_factor(half_sum(e2), energy1, denoiseBound, priorSpeechProb);
   }
 
   // ---- synthesis window, overlap-add, emit 160, carry 96 (ns_core.c:1344-1359)

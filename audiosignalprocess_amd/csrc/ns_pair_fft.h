@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include "ns_device.h"
-#include "ns_layout.h"
 
 namespace aspns_pair {
 using namespace aspns_dev;

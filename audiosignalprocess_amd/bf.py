@@ -80,6 +80,7 @@ def load_library():
             "AspBfBatch_SetTables": [vp, ip, vp, ip],
             "AspBfBatch_SetStream": [vp, vp],
             "AspBfBatch_Synchronize": [vp],
+            "AspBf_debug_hypotf": [vp, vp, vp, C.c_size_t, ip],
         }
         _declare(lib, sig)
         lib.AspBf_state_size.argtypes = []

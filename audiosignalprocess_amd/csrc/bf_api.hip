@@ -39,6 +39,11 @@ struct AspBfBatch {
 };
 
 namespace {
+__global__ void bf_debug_hypotf_kernel(const float* x, const float* y, float* out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = bf_hypotf(x[i], y[i]);
+}
+
 int upload_tables(AspBfBatch* b) {
   std::vector<float> pack;
   pack_tables(b->h, pack);
@@ -257,6 +262,25 @@ int AspBfBatch_Synchronize(AspBfBatch* b) {
   AspDeviceScope dev_scope_;
   BF_TRY(dev_scope_.select(b->device));
   BF_TRY(hipStreamSynchronize(b->stream));
+  return ASP_OK;
+}
+
+// Test seam for the device math: out[i] = bf_hypotf(x[i], y[i]) evaluated on the device.
+int AspBf_debug_hypotf(const float* x, const float* y, float* out, size_t n, int device) {
+  if (!x || !y || !out || n == 0 || n > ((size_t)1 << 30)) return bf_fail(ASP_ERR_PARAM, "AspBf_debug_hypotf: bad argument");
+  AspDeviceScope dev_scope_;
+  if (int rc = dev_scope_.select("asp_bf", device, ASP_ERR_NO_DEVICE, "AspBf_debug_hypotf: no HIP device")) return rc;
+  float* d = nullptr;  // x [n], y [n], out [n]
+  BF_TRY(hipMalloc((void**)&d, 3 * n * sizeof(float)));
+  hipError_t e = hipMemcpy(d, x, n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + n, y, n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(bf_debug_hypotf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d, d + n, d + 2 * n, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return bf_fail(ASP_ERR_HIP, "AspBf_debug_hypotf", e);
   return ASP_OK;
 }
 

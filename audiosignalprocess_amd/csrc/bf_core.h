@@ -388,6 +388,20 @@ inline cf trace(const cf* mat, int M) {
   for (int i = 0; i < M; ++i) t += mat[i * M + i];
   return t;
 }
+// 1.f / z as the reference's build divides complex<float> (libgcc's __divsc3: Smith's algorithm, the larger
+// component of z divides first), for the finite non-zero divisors of these tables (a norm, a trace: the imaginary
+// part is exactly 0, so this is 1.f / z.real()).  Written out because the quotient is the complex runtime's
+// otherwise: compiler-rt's __divsc3, which hipcc links into the library, forms c * c + d * d in float and gives
+// other tables at 2, 3, 6 and 8 microphones.
+inline cf recip(cf z) {
+  const float a = 1.f, b = 0.f, c = z.real(), d = z.imag();
+  if (fabsf(c) < fabsf(d)) {
+    const float ratio = c / d, denom = c * ratio + d;
+    return cf((a * ratio + b) / denom, (b * ratio - a) / denom);
+  }
+  const float ratio = d / c, denom = d * ratio + c;
+  return cf((b * ratio + a) / denom, (b - a * ratio) / denom);
+}
 template <typename S>
 inline void scale(cf* mat, int count, const S& scalar) {
   for (int i = 0; i < count; ++i) mat[i] *= scalar;
@@ -466,7 +480,7 @@ inline const char* make_tables(HostTables& h, BfParams& p, int num_mics, const f
     cf dot = cf(0.f, 0.f);
     for (int i = 0; i < M; ++i) dot += std::conj(d[i]) * d[i];
     const cf norm_factor = std::sqrt(dot);
-    scale(d, M, 1.f / norm_factor);
+    scale(d, M, recip(norm_factor));
   }
   // InitTargetCovMats
   for (int i = 0; i < kBins; ++i) {
@@ -476,14 +490,14 @@ inline const char* make_tables(HostTables& h, BfParams& p, int num_mics, const f
     else
       boxcar(wave_numbers[i], M, mic_spacing, kBoxcarHalfWidth, m);
     const cf normalization_factor = trace(m, M);
-    scale(m, MM, 1.f / normalization_factor);
+    scale(m, MM, recip(normalization_factor));
   }
   // InitInterfCovMats
   {
     cf* m = &icov[0];
     dc_covariance(M, kCovUniformGapHalfWidth, m);
     const cf normalization_factor = trace(m, M);
-    scale(m, MM, 1.f / normalization_factor);
+    scale(m, MM, recip(normalization_factor));
   }
   std::vector<cf> uniform(MM), angled(MM), box(MM), vec(M), vec_t(M);
   for (int i = 1; i < kBins; ++i) {
@@ -508,9 +522,9 @@ inline const char* make_tables(HostTables& h, BfParams& p, int num_mics, const f
         angled[r * M + c] = cur_element;
       }
     cf normalization_factor = trace(uniform.data(), M);
-    scale(uniform.data(), MM, 1.f / normalization_factor);
+    scale(uniform.data(), MM, recip(normalization_factor));
     normalization_factor = trace(angled.data(), M);
-    scale(angled.data(), MM, 1.f / normalization_factor);
+    scale(angled.data(), MM, recip(normalization_factor));
     scale(uniform.data(), MM, 1 - kBalance);
     scale(angled.data(), MM, kBalance);
     cf* m = &icov[(size_t)i * MM];

@@ -90,6 +90,10 @@ int AspBfBatch_SetTables(AspBfBatch* b, int which, const float* in, int count);
 int AspBfBatch_SetStream(AspBfBatch* b, void* hip_stream);
 int AspBfBatch_Synchronize(AspBfBatch* b);
 
+/* Test seam: out[i] = the kernel's hypotf (std::abs of a complex<float>) of (x[i], y[i]), evaluated on the
+ * device.  x, y and out are host pointers to n floats. */
+int AspBf_debug_hypotf(const float* x, const float* y, float* out, size_t n, int device);
+
 #ifdef __cplusplus
 }
 #endif

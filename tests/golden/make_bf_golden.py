@@ -10,6 +10,7 @@ WebRtc_rdft because openmax_dl is absent from it):
         $R/webrtc/system_wrappers/source/aligned_malloc.cc $R/webrtc/base/checks.cc \
         tests/golden/bf_ref_shim.cc bf_fft4g.o -o libbf_ref.so
     python tests/golden/make_bf_golden.py libbf_ref.so
+    python tests/golden/make_bf_golden.py libbf_ref.so --edges
 
 tests/golden/bf_omx/ holds the stand-in omxSP.h; bf_ref_shim.cc defines its four functions on WebRtc_rdft and
 starts high_pass_postfilter_mask_, which the reference never initialises, at 0.
@@ -23,9 +24,14 @@ Before anything is written: the seam's forward transform agrees with numpy.fft.r
 the block's peak magnitude and forward-then-inverse returns the block to the same tolerance; and the coverage
 below, asserted on the reference alone (check_coverage).  A second instance of the reference (`probe`: it forgets
 the previous block before every block, so ApplyDecay is skipped) is fed the same input to see the masks before
-the decay."""
+the decay.
+
+--edges writes tests/golden/bf_edges_golden.npz instead, from bf_runs.EDGE_RUNS: the same per-run entries, and in
+the same file the tables, bin bounds and spacing of every geometry the other tables file does not hold.  Asserted on
+the reference alone before it is written (check_edges): every mask it logs is finite; the outputs of the scaled
+families a, b1, b2 and c are not all zero; silence from the first chunk (family h) gives masks of exactly 1 and
+outputs of exactly 0; 5, 6 and 7 microphones and every family occur; all four frame_offset_ values occur."""
 import ctypes as C
-import hashlib
 import os
 import sys
 
@@ -35,7 +41,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 from audiosignalprocess_amd.bf import BINS, BUFFER, TABLES, table_length  # noqa: E402
-from tests.bf_runs import CHUNKS, RUNS, geometry, inputs, replay  # noqa: E402
+from tests.bf_runs import (CHUNKS, EDGE_RUNS, FAMILIES, RUNS, geometry, inputs, inputs_sha256, replay,  # noqa: E402
+                           table_key)
 
 P, IP = C.c_void_p, C.c_int
 MID_LO = 4   # bins below the mid band carry the low-frequency mean, not their own mask
@@ -161,30 +168,43 @@ def check_coverage(refs, tps, scal, xs):
     assert {r.M for r in refs} >= {2, 3, 4, 8}
 
 
-def main(path):
-    L = load(path)
-    check_seam(L)
-    out = {"num_runs": np.array([len(RUNS)], np.int32), "chunks": np.array([CHUNKS], np.int32)}
-    tables = {}
-    refs, tps, scal, xs = [], [], [], []
-    for r, spec in enumerate(RUNS):
+def check_edges(refs, specs, outs, scal):
+    """On the reference alone."""
+    for bf, spec, (y, hy) in zip(refs, specs, outs):
+        raw, final = np.concatenate(bf.raw), np.concatenate(bf.final)
+        what = "run with %d microphones, family %s: " % (spec["mics"], spec["family"])
+        assert np.isfinite(raw).all() and np.isfinite(final).all(), what + "every mask the reference logs is finite"
+        assert np.isfinite(y).all() and (hy is None or np.isfinite(hy).all()), what + "every output sample is finite"
+        if spec["family"] in ("a", "b1", "b2", "c"):
+            assert y.any() and hy.any(), what + "the outputs are not all zero"
+        if spec["family"] == "h":
+            assert (raw == 1.0).all() and (final == 1.0).all(), what + "every mask is exactly 1"
+            assert not y.any() and not hy.any(), what + "every output is exactly 0"
+    assert {s["mics"] for s in specs if s["family"] is None} >= {5, 6, 7}
+    assert {s["family"] for s in specs} >= set(FAMILIES)
+    assert {s["family"] for s in specs if s["mics"] == 7} >= {"a", "b1", "b2", "c", "e"}
+    assert set(np.concatenate([sc[:, 0] for sc in scal])) == {0, 32, 64, 96}, "all four frame_offset_ values occur"
+
+
+def run_all(L, specs, out, tables, known=()):
+    """Replays `specs` on the reference into `out` (per run) and `tables` (per geometry not in `known`)."""
+    refs, tps, scal, xs, outs = [], [], [], [], []
+    for r, spec in enumerate(specs):
         x, hi = inputs(spec)
-        h = hashlib.sha256(np.ascontiguousarray(x).tobytes())
-        if hi is not None:
-            h.update(np.ascontiguousarray(hi).tobytes())
         bf = Ref(L)
         y, hy, tp, sc = replay(spec, bf)
-        out["r%d_inputs_sha256" % r] = np.array(h.hexdigest())
+        out["r%d_inputs_sha256" % r] = np.array(inputs_sha256(x, hi))
         out["r%d_out" % r] = y
         if hy is not None:
             out["r%d_high_out" % r] = hy
         out["r%d_target_present" % r] = tp
         out["r%d_scalars" % r] = sc
+        assert set(bf.snaps) == set(spec["snaps"])
         for f, snap in bf.snaps.items():
             for k, v in snap.items():
                 out["r%d_s%d_%s" % (r, f, k)] = v
-        key = "m%d_d%s" % (spec["mics"], ("%g" % spec["spacing"]).replace(".", "p"))
-        if key + "_window" not in tables:
+        key = table_key(spec)
+        if key + "_window" not in tables and key not in known:
             for name, t in zip(TABLES, bf.tables()):
                 assert t.size == table_length(TABLES.index(name), spec["mics"])
                 tables[key + "_" + name] = t
@@ -198,15 +218,41 @@ def main(path):
         tps.append(tp)
         scal.append(sc)
         xs.append(x)
+        outs.append((y, hy))
         print("run", r, "target present on", int(tp.sum()), "of", len(tp), "chunks; median raw mask %.3f" %
               float(np.median(np.concatenate(bf.raw))))
+    return refs, tps, scal, xs, outs
+
+
+def save(name, data):
+    dst = os.path.join(HERE, name)
+    np.savez_compressed(dst, **data)
+    print(dst, os.path.getsize(dst), "bytes")
+    assert os.path.getsize(dst) < 1000000
+
+
+def main(path):
+    L = load(path)
+    check_seam(L)
+    out = {"num_runs": np.array([len(RUNS)], np.int32), "chunks": np.array([CHUNKS], np.int32)}
+    tables = {}
+    refs, tps, scal, xs, _ = run_all(L, RUNS, out, tables)
     check_coverage(refs, tps, scal, xs)
-    for name, data in (("bf_golden.npz", out), ("bf_tables_golden.npz", tables)):
-        dst = os.path.join(HERE, name)
-        np.savez_compressed(dst, **data)
-        print(dst, os.path.getsize(dst), "bytes")
-        assert os.path.getsize(dst) < 1000000
+    save("bf_golden.npz", out)
+    save("bf_tables_golden.npz", tables)
+
+
+def main_edges(path):
+    L = load(path)
+    check_seam(L)
+    out = {"num_runs": np.array([len(EDGE_RUNS)], np.int32),
+           "chunks": np.array([s["chunks"] for s in EDGE_RUNS], np.int32),
+           "mics": np.array([s["mics"] for s in EDGE_RUNS], np.int32),
+           "families": np.array([s["family"] or "" for s in EDGE_RUNS])}
+    refs, tps, scal, xs, outs = run_all(L, EDGE_RUNS, out, out, known={table_key(s) for s in RUNS})
+    check_edges(refs, EDGE_RUNS, outs, scal)
+    save("bf_edges_golden.npz", out)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    (main_edges if "--edges" in sys.argv[2:] else main)(sys.argv[1])

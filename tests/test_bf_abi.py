@@ -17,7 +17,7 @@ INCLUDE = os.path.join(ROOT, "include")
 def test_every_declared_symbol_is_exported(built_lib):
     lib = C.CDLL(built_lib)
     names = declared_functions("asp_bf.h")
-    assert len(names) == 15 and all(n.startswith("AspBf") for n in names)
+    assert len(names) == 16 and all(n.startswith("AspBf") for n in names)
     assert [n for n in names if not hasattr(lib, n)] == []
 
 
@@ -28,7 +28,7 @@ def test_python_mirror_matches_the_header_prototypes(built_lib):
     txt = open(os.path.join(INCLUDE, "asp_bf.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     protos = dict(re.findall(r"\b(AspBf\w+)\s*\(([^;{]*)\)\s*;", txt))
-    assert len(protos) == 15
+    assert len(protos) == 16
     for name, args in protos.items():
         n = 0 if args.strip() == "void" else args.count(",") + 1
         assert len(getattr(lib, name).argtypes) == n, name

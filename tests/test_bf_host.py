@@ -13,7 +13,7 @@ import pytest
 
 from audiosignalprocess_amd import bf
 from audiosignalprocess_amd.synth import bf_chunks
-from tests.bf_runs import ARRAYS, CHUNKS, RUNS, geometry, inputs, replay, state_scalars
+from tests.bf_runs import ARRAYS, CHUNKS, RUNS, geometry, hypot_operands, inputs, replay, state_scalars, table_key
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -21,10 +21,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def same(a, b):
     a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def table_key(spec):
-    return "m%d_d%s" % (spec["mics"], ("%g" % spec["spacing"]).replace(".", "p"))
 
 
 @pytest.fixture(autouse=True, scope="module")
@@ -116,25 +112,14 @@ def test_hypotf_is_the_host_libms():
     libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
     libm.hypotf.restype = C.c_float
     libm.hypotf.argtypes = [C.c_float, C.c_float]
-    rng = np.random.default_rng(11)
-    n = 1 << 20
-    wide = rng.integers(0, 0x7f800000, size=(2, n), dtype=np.int64).astype(np.uint32)
-    wide |= rng.integers(0, 2, size=(2, n), dtype=np.int64).astype(np.uint32) << np.uint32(31)
-    wide = wide.view(np.float32)
-    audio = (rng.standard_normal((2, n)) * np.exp(rng.uniform(-20, 12, (2, n)))).astype(np.float32)
-    tiny = np.float32(1e-45)
-    e = np.array([0.0, -0.0, tiny, -tiny, 3 * tiny, 1.1754942e-38, 1.17549435e-38, 1.0, 3.0, 4.0, 1e-20, 1e20,
-                  3.4028235e38, 2.0e38, np.inf, -np.inf], np.float32)
-    ex, ey = [a.ravel() for a in np.meshgrid(e, e)]
-    x = np.concatenate([wide[0], audio[0], ex, audio[1][:4096]])
-    y = np.concatenate([wide[1], audio[1], ey, audio[1][:4096]])   # the last 4096: equal components
+    x, y, edges = hypot_operands()
     got = np.zeros(x.size, np.float32)
     bf.Restate.lib().BfRestate_hypotf(x.ctypes.data, y.ctypes.data, got.ctypes.data, x.size)
     assert x.size >= 1000000
     # libm through numpy: np.hypot on float32 calls hypotf; spot-check that against ctypes
     with np.errstate(over="ignore"):
         want = np.hypot(x, y)
-    for i in list(range(0, x.size, 50021)) + list(range(2 * n, 2 * n + ex.size)):
+    for i in list(range(0, x.size, 50021)) + list(edges):
         assert np.float32(libm.hypotf(float(x[i]), float(y[i]))).view(np.uint32) == want[i].view(np.uint32)
     bad = np.nonzero(got.view(np.uint32) != want.view(np.uint32))[0]
     assert bad.size == 0, (bad[:5], x[bad[:5]], y[bad[:5]], got[bad[:5]], want[bad[:5]])

@@ -232,8 +232,10 @@ int AspAgcBatch_Create(AspAgcBatch** out, int num_streams, int device) {
   hipError_t e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipMalloc((void**)&b->state, sizeof(AspAgcState) * (size_t)num_streams);
   if (e == hipSuccess) e = hipMalloc((void**)&b->level, sizeof(int32_t) * (size_t)num_streams);
-  if (e == hipSuccess) e = hipMemset(b->state, 0, sizeof(AspAgcState) * (size_t)num_streams);
-  if (e == hipSuccess) e = hipMemset(b->level, 0, sizeof(int32_t) * (size_t)num_streams);
+  // on the batch's own (non-blocking) stream: a null-stream memset is not ordered with the copies Init puts on it
+  if (e == hipSuccess) e = hipMemsetAsync(b->state, 0, sizeof(AspAgcState) * (size_t)num_streams, b->own_stream);
+  if (e == hipSuccess) e = hipMemsetAsync(b->level, 0, sizeof(int32_t) * (size_t)num_streams, b->own_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(b->own_stream);
   if (e != hipSuccess) {
     AspAgcBatch_Free(b);
     return agc_fail(ASP_ERR_HIP, "AspAgcBatch_Create", e);

@@ -1232,3 +1232,57 @@ def test_metrics_bursty_far_end_vs_oracle(aec):
         assert np.allclose(fa[37:44], fb[37:44], atol=1e-2, equal_nan=True)          # ERLE: behind the NLP (NaN included)
     assert np.array_equal(g.get_metrics()[:, 4:8], np.array([o.get_metrics().to_tuple()[4:8] for o in orc]))
     assert nan_frames > 0, "this input is meant to reach the reference's NaN case"
+
+
+def test_same_input_through_every_issuer(aec):
+    """One input through every way a control step's work reaches the device (aec_api.hip, DeviceIssuer: launch, hand-off
+    record, stream record; the fourth, none, issues nothing): (a) plain launches, BufferFarend + Process per frame;
+    (b) Run with the hand-off build; (c) Run without it (plain launches with the far-end work deferred into each
+    Process launch); (d) per-stream control, BufferFarend + ProcessV with the same delay on every
+    stream.  5 streams (a ragged workgroup), 200 frames, reported delay 40 ms jumping to 90 ms at frame 130: start-up
+    end, a far-pointer move, steady state.  Outputs and the whole state of (a), (b), (c) are equal bit for bit, and
+    so are those of (d): its kernels run the same block code on the same descriptors, read from device memory
+    (measured equal before the control plane was split; test_handoff_build_equals_plain_launches holds the same bar
+    between (b) and (c)).  (d)'s control plane of every stream equals (a)'s."""
+    from audiosignalprocess_amd.ns import DeviceBuffer
+
+    S, F, J = 5, 200, 130
+    far, near = aec_frames(S, F)
+    delay = lambda f: 40 if f < J else 90
+    outs, batches = {}, {}
+    g = batches["a"] = aec.AecBatch(S)
+    outs["a"] = np.stack([g.frame(far[f], near[f], delay(f))[0] for f in range(F)])
+    # Run on device buffers: there a hand-off build that cannot get its resources is an error, not a quiet fall-back
+    per = S * 160 * 4
+    df, dn = DeviceBuffer(far.nbytes), DeviceBuffer(near.nbytes)
+    df.upload(far)
+    dn.upload(near)
+    for key, flow in (("b", 1), ("c", 0)):
+        g = batches[key] = aec.AecBatch(S)
+        g.set_flow(flow)
+        do = DeviceBuffer(near.nbytes)
+        g.run_device(df.ptr, dn.ptr, do.ptr, 160, J, delay(0))
+        g.run_device(df.ptr + J * per, dn.ptr + J * per, do.ptr + J * per, 160, F - J, delay(J))
+        g.synchronize()
+        outs[key] = do.download(near.shape)
+    g = batches["d"] = aec.AecBatch(S)
+    out_d = np.empty_like(near)
+    for f in range(F):
+        assert g.buffer_farend(far[f]) == 0
+        out_d[f], status = g.process_v(near[f], [delay(f)] * S)
+        assert not status.any(), f
+    outs["d"] = out_d
+    assert np.isfinite(outs["a"]).all() and np.abs(outs["a"][-50:]).max() > 0
+    ca = batches["a"].control()
+    assert ca.startup_phase == 0 and ca.knownDelay > 0            # past start-up, the delay jump has been followed
+    for key in "bcd":
+        assert np.array_equal(_bits(outs[key]), _bits(outs["a"])), key
+        for s in range(S):
+            rep = _state_report(batches[key].export_state(s), batches["a"].export_state(s))
+            assert all(v[0] for v in rep.values()), (key, s, {k: v for k, v in rep.items() if not v[0]})
+    for s in range(S):
+        cd = batches["d"].control_stream(s)
+        for name, _t in ca._fields_:
+            assert getattr(cd, name) == getattr(ca, name), (s, name)
+    for g in batches.values():
+        g.close()

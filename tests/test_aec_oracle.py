@@ -340,6 +340,79 @@ def test_host_control_plane_matches_oracle():
         assert lib.AspAecBatch_Free(h) == 0
 
 
+PER_STREAM_BASE = [0, 0, 20, 40, 60, 100, 5, 0, 250, 30, 80, 10]
+
+
+def per_stream_delay(s, f):
+    """The reported-delay schedule of the per-stream control tests (here and tests/test_aec_gpu.py's
+    test_per_stream_delays_and_reinit_vs_one_oracle_per_stream): a jump, an out-of-range and a negative delay."""
+    d = PER_STREAM_BASE[s]
+    if s == 1 and f >= 130:
+        d = 90
+    if s == 4 and 200 <= f < 210:
+        d = 700
+    if s == 7 and f == 250:
+        d = -5
+    return d
+
+
+@pytest.mark.parametrize("ext", [0, 1])
+def test_per_stream_control_plane_matches_oracle(ext):
+    """Per-stream control (AspAecBatch_ProcessV / _InitStream / the uniform Process on top of it) on a control-only
+    handle: twelve streams on the delay schedule of the GPU test, one re-initialised at frame 170, every stream
+    against its own oracle -- the return value of every call and every control-plane field after every call."""
+    import ctypes as C
+
+    from audiosignalprocess_amd import aec as aec_mod
+    from audiosignalprocess_amd._abi import AspAecControl
+
+    lib = aec_mod._lib()
+    lib.AspAecBatch_CreateControlOnly.argtypes = [C.POINTER(C.c_void_p), C.c_int]
+    S, F, n = 12, 460, 160
+    h = C.c_void_p()
+    assert lib.AspAecBatch_CreateControlOnly(C.byref(h), S) == 0
+    assert lib.AspAecBatch_Init(h, 16000, 48000) == 0
+    oras = [oracle_lib.OracleAec(16000) for _ in range(S)]
+    if ext:
+        assert lib.AspAecBatch_enable_delay_correction(h, 1) == 0
+        for o in oras:
+            o.enable_delay_correction(1)
+    dummy = np.zeros(S * n, np.float32)
+    z = np.zeros(n, np.float32)
+    status = np.zeros(S, np.int32)
+    cb = AspAecControl()
+    for f in range(F):
+        if f == 170:
+            assert lib.AspAecBatch_InitStream(h, 5) == 0
+            oras[5] = oracle_lib.OracleAec(16000)
+            if ext:
+                oras[5].enable_delay_correction(1)
+        uniform = 300 <= f < 320
+        delays = [35 if uniform else per_stream_delay(s, f) for s in range(S)]
+        assert lib.AspAecBatch_BufferFarend(h, dummy.ctypes.data, n, 1) == 0
+        if uniform:
+            rc = lib.AspAecBatch_Process(h, dummy.ctypes.data, dummy.ctypes.data, n, 35, 0, 1)
+            status[:] = rc
+        else:
+            ms = np.asarray(delays, np.int16)
+            rc = lib.AspAecBatch_ProcessV(h, dummy.ctypes.data, dummy.ctypes.data, n, ms.ctypes.data, None,
+                                          status.ctypes.data, 1)
+        assert rc in (0, -1), (ext, f, rc)
+        for s in range(S):
+            rc_o = oras[s].frame(z, z, delays[s])[1]
+            assert status[s] == rc_o, (ext, f, s)
+            assert lib.AspAecBatch_GetControlStream(h, s, C.byref(cb)) == 0
+            _, co = oras[s].export()
+            for name, _t in cb._fields_:
+                assert getattr(cb, name) == getattr(co, name), (ext, f, s, name)
+    far_reads = set()
+    for s in range(S):
+        assert lib.AspAecBatch_GetControlStream(h, s, C.byref(cb)) == 0
+        far_reads.add(cb.far_read)
+    assert len(far_reads) > 3          # the streams did move apart
+    assert lib.AspAecBatch_Free(h) == 0
+
+
 def _aec_band_frames(F, seed=5):
     """Far / near low band as the 16 kHz generator, plus a high band that carries echo-like and
     independent content (int16-range floats)."""

@@ -14,6 +14,7 @@
 //     state row; bin 128 is computed on every lane (wave-uniform) and committed with the scalars;
 //   * per-stream scalars are wave-uniform: read from the scalar row with v_readlane, every
 //     data-independent branch of the reference is a scalar branch, written back with v_writelane;
+//     the hand-off build's product kernels keep the float scalars and most row tails in the wave's LDS image (ScalarRow);
 //   * independent wave-uniform chains with one formula are evaluated ONCE, each on its own lane: bin 128 of the three
 //     quantile trackers on lanes 48..50 of the scalar row, the flatness feature's exp beside bin 128's exp(-logLrt) --
 //     each value through the operations of its wave-uniform pass (bit-identical), no LDS, no barrier;
@@ -90,7 +91,8 @@ __device__ __forceinline__ const P* ns_cold(const P* p) {  // (a wave-uniform po
 // V_AVGPAUSE -- lives in an LDS image of the wave for the length of the walk.  The wave copies it in once behind the
 // chunk's wait, every step goes through the image (StateAcc), and after the walk's last step the wave writes the image
 // back (sc1), drains and publishes seq[stream] = want + (the walk's end): once per walk.  Between two of its own steps
-// a wave neither drains nor publishes; the scalar row stays in its register.  What stays in memory inside a walk -- the
+// a wave neither drains nor publishes; the scalar row's integer slots stay in its register, the float ones in the image
+// (ScalarRow).  What stays in memory inside a walk -- the
 // start-up rows V_INITMAGN / V_PARAMNOISE and the histograms -- is read back only in rare paths, which wait for the
 // wave's outstanding stores themselves.  Each wave touches only its own image: no barrier is added.
 struct NsFlowArgs {
@@ -195,6 +197,60 @@ struct StateAcc {
       const f32x4v v = *reinterpret_cast<const lds_f32x4*>(img + i * 256 + 4 * lane);
       sc1_store4(rs, lane * 16, i * 1024, make_float4(v.x, v.y, v.z, v.w));
     }
+  }
+};
+
+// The scalar row of a stream (ns_layout.h: 64 dwords, the per-stream scalars and the bin-128 row tails): who holds the
+// master copy of slot K inside a step, behind one seam.  `sv` is the row on the lanes of one vector register.
+//   * IMG = false (the plain build, and the diagnostic kernels of both builds): `sv` holds every slot; a read is a
+//     v_readlane, a float write a v_cndmask under a one-lane mask;
+//   * IMG = true (the product kernels of the hand-off build): `sv` holds the integer scalars (slots below S_OVERDRIVE)
+//     and the three trackers' bin-128 members (lquantile and density tails, lane-resident by design); every other slot
+//     -- the float scalars and the other row tails -- has its master in the wave's LDS image, where the row lies
+//     anyway.  A read is an LDS read at a wave-uniform address (every lane receives the value; contiguous slots as one
+//     8- or 16-byte read), a write an LDS store: neither is a vector-ALU instruction, which is what bounds the step.
+//     The values arrive in vector registers -- where the plain form has them in scalar ones -- and are wave-uniform in
+//     fact; the step reads each in front of its first use.  `sv`'s lanes of image-owned slots are stale inside a walk
+//     and are never stored (store_owned).
+// Both bodies of the step come from one text, so both use the same master for every slot.  The diagnostic kernels stay
+// with IMG = false: their stamp points already hold them at 128 vector registers, and the image form needs about eight
+// more at the step's widest point (profiles/README.md); what they time is the step with the plain row traffic.
+template <bool IMG>
+struct ScalarRow {
+  lds_f32* row;  // hand-off build: the image's scalar row (a wave-uniform address)
+  static constexpr int kTrk0 = aspns::S_TAIL0 + aspns::V_LQ0, kTrk1 = aspns::S_TAIL0 + aspns::V_DEN2;
+  static constexpr bool in_image(int k) { return IMG && k >= aspns::S_OVERDRIVE && !(k >= kTrk0 && k <= kTrk1); }
+  __device__ __forceinline__ explicit ScalarRow(float* image) : row((lds_f32*)image + aspns::kOffScalars) {}
+  template <int K>
+  __device__ __forceinline__ float f(float sv) const {
+    if constexpr (in_image(K)) return row[K];
+    else return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), K));
+  }
+  // slots K .. K + N - 1 (N = 2 or 4, K a multiple of N: one aligned LDS read where the image is the master)
+  template <int K, int N>
+  __device__ __forceinline__ void ld(float sv, float (&v)[N]) const {
+    static_assert((N == 2 || N == 4) && K % N == 0 && in_image(K) == in_image(K + N - 1), "one aligned group, one master");
+    if constexpr (in_image(K) && N == 2) {
+      const f32x2v t = *reinterpret_cast<const lds_f32x2*>(row + K);
+      v[0] = t.x; v[1] = t.y;
+    } else if constexpr (in_image(K)) {
+      const f32x4v t = *reinterpret_cast<const lds_f32x4*>(row + K);
+      v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+#pragma unroll
+      for (int i = 0; i < N; ++i) v[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), K + i));
+    }
+  }
+  // a wave-uniform float value into slot K.  IMG: every lane that executes stores the same value to the same address
+  // (the step's commit runs on lane 0 alone, the rare paths on all 64)
+  template <int K>
+  __device__ __forceinline__ void set(float& sv, float val) const {
+    if constexpr (in_image(K)) row[K] = val;
+    else sv = setlane_vgpr<K>(sv, val);
+  }
+  // the walk's end (hand-off build): the lanes `sv` owns go back to the image, the others are already there
+  __device__ __forceinline__ void store_owned(int lane, float sv) const {
+    if (!IMG || lane < aspns::S_OVERDRIVE || (lane >= kTrk0 && lane <= kTrk1)) row[lane] = sv;
   }
 };
 
@@ -356,12 +412,19 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
     }
   };
 
-  // ---- scalars: lane k holds scalar k (wave-uniform values, read with v_readlane)
+  // ---- scalars: lane k holds scalar k (wave-uniform values, read with v_readlane); the hand-off build keeps the
+  // float scalars and most row tails in the image instead (ScalarRow)
   float sv;
+  constexpr bool ROW_IMG = FLOW && !DIAG;  // who holds the float scalars and the row tails (ScalarRow)
+  const ScalarRow<ROW_IMG> srow(imgs[FLOW ? wv : 0]);
 #define SC_I(k) __builtin_amdgcn_readlane(__float_as_int(sv), (k))
-#define SC_F(k) __int_as_float(SC_I(k))
+#define SC_F(k) srow.template f<(k)>(sv)
 #define SC_SET_I(k, val) sv = writelane_bits<(k)>(sv, (int)(val))
-#define SC_SET_F(k, val) sv = setlane_vgpr<(k)>(sv, (val))
+#define SC_SET_F(k, val) srow.template set<(k)>(sv, (val))
+  // (the steady body commits its integer scalars as two carry adds on `sv` under constant lane masks, addlanes_bits:
+  // blockInd and the three counters + 1, mup3 - 1, updates and updateParsFlag unchanged -- a step of the steady body
+  // resets no counter and closes no window)
+  static_assert(S_COUNTER1 == S_COUNTER0 + 1 && S_COUNTER2 == S_COUNTER0 + 2, "the three counters: consecutive lanes");
   // ---- sliding analysis buffer [96 carried | 160 new]: lane L owns samples 4L .. 4L+3
   float4 s4;
   // syntBuf[0..95]: the lane's output samples 2E, 2E+1 that still carry overlap are those of
@@ -455,6 +518,13 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
     sa.st2(kOffVec + (f)*kVecStride, 2 * lane, srcv[0], srcv[1]);                              \
     SC_SET_F(S_TAIL0 + (f), srcv[2]);                                                          \
   }
+  // the same for the five rows every step writes: the hand-off build stores their tails with the step's float scalars,
+  // on one lane (commit_floats)
+#define STORE3_HOT(f, srcv)                                                                    \
+  {                                                                                            \
+    sa.st2(kOffVec + (f)*kVecStride, 2 * lane, srcv[0], srcv[1]);                              \
+    if constexpr (!ROW_IMG) SC_SET_F(S_TAIL0 + (f), srcv[2]);                                  \
+  }
   // the frame of the chunk's next step is requested while this step still has its inverse transform ahead
 #define NS_NEXT_FRAME()                                                                        \
   if constexpr (FLOW) {                                                                        \
@@ -471,7 +541,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
     if (walk_done_) {                                                                          \
       NS_BUDGET_ASIDE()                                                                        \
       const int lane_w_ = ns_cold(lane);                                                       \
-      sa.st1(kOffScalars, lane_w_, sv);                                                        \
+      srow.store_owned(lane_w_, sv);                                                           \
       lds_sync1();                                                                             \
       sa.image_write_back(lane_w_);                                                            \
       handoff_drain();                                                                         \
@@ -539,8 +609,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
     // transform, the magnitudes and the logarithms
     LOADV(LQ[0], V_LQ0) LOADV(LQ[1], V_LQ1) LOADV(LQ[2], V_LQ2)
     LOADV(DEN[0], V_DEN0) LOADV(DEN[1], V_DEN1) LOADV(DEN[2], V_DEN2)
-    LOADV(quant, V_QUANT)
-    LOADT(quant, V_QUANT)  // (the trackers' bin-128 members stay on their lanes of the scalar row: phase 4)
+    LOADV(quant, V_QUANT)  // (the trackers' bin-128 members stay on their lanes of the scalar row: phase 4)
     NS_STAMP(1)
     // ---- forward FFT (ns_core.c:886-911)
     *reinterpret_cast<float4*>(&tile[2 * lane]) = make_float4(wx0, wx1, wx2, wx3);
@@ -557,8 +626,8 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
     // second group of state rows (latency hides under magnitude / log / trackers)
     LOADV(magnPrevA, V_MAGNPREV_A) LOADV(logLrt, V_LOGLRT) LOADV(avgPause, V_AVGPAUSE)
     LOADV(smooth, V_SMOOTH) LOADV(noisePrev, V_NOISEPREV)
-    LOADT(magnPrevA, V_MAGNPREV_A) LOADT(logLrt, V_LOGLRT) LOADT(avgPause, V_AVGPAUSE)
-    LOADT(smooth, V_SMOOTH) LOADT(noisePrev, V_NOISEPREV)
+    // (their bin-128 members are read from the scalar row where they are first used: wave-uniform values that the
+    // hand-off build holds in vector registers, which the transform's end has none to spare of)
 
     float re[NS3], im[NS3], magn[NS3];
     re[0] = er.x;
@@ -602,9 +671,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       if constexpr (STEADY) ns_assume_steady(ss);
       if constexpr (DIAG) diag_steps += STEADY ? 1u : 0x10000u;
       const int blockInd = ss.blockInd;
-      const float overdrive = SC_F(S_OVERDRIVE);
-      const float denoiseBound = SC_F(S_DENOISEBOUND);
-      float priorSpeechProb = SC_F(S_PRIORSPEECHPROB);
+      float priorSpeechProb;  // (read in front of the tanh of phase 9; overdrive and denoiseBound: phase 11)
       const int gainmap = ss.gainmap;
 
       float noise[NS3], prevStsa[NS3];
@@ -612,8 +679,44 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       int updates = ss.updates;
       int counter[3] = {ss.counter[0], ss.counter[1], ss.counter[2]};
 
+      // Bin 128 of ComputeSnr (ns_core.c:566-588; the lane's two bins: phase 6), every value through the operations of
+      // the per-bin loop.  noise2: bin 128 of the noise estimate.
+      float snrLocPost[NS3], snrLocPrior[NS3];
+      auto snr_tail = [&](float noise2) __attribute__((always_inline)) {
+        const float q1t = fdiv(magnPrevA[2], noisePrev[2] + 0.0001f);
+        const float q2t = fdiv(magn[2], noise2 + 0.0001f);  // used where magn > noise
+        const float previousEstimateStsa = q1t * smooth[2];
+        prevStsa[2] = previousEstimateStsa;
+        snrLocPost[2] = 0.f;
+        if (magn[2] > noise2) snrLocPost[2] = q2t - 1.f;
+        snrLocPrior[2] = NS_DD_PR_SNR * previousEstimateStsa + (1.f - NS_DD_PR_SNR) * snrLocPost[2];
+      };
+      auto load_snr_tails = [&]() __attribute__((always_inline)) {
+        static_assert(V_SMOOTH == V_QUANT + 1 && V_MAGNPREV_A == V_NOISEPREV + 1, "row tails read as pairs");
+        float t2[2], u2[2];
+        srow.template ld<S_TAIL0 + V_QUANT, 2>(sv, t2);
+        srow.template ld<S_TAIL0 + V_NOISEPREV, 2>(sv, u2);
+        quant[2] = t2[0]; smooth[2] = t2[1];
+        noisePrev[2] = u2[0]; magnPrevA[2] = u2[1];
+      };
+      // The step's two logarithms of bin 128 -- log magn (here) and log(1 + 2 snrLocPrior) (phase 8) -- share ONE third
+      // slot in the steady body: no tracker publishes and the start-up model is off, so the noise estimate of bin 128 is
+      // the stored quantile and the second argument needs only magn[2] and loaded state.  It is computed ahead, goes on
+      // lane 1 of this call's third slot beside magn[2] on the other lanes, and both results come back by broadcast; the
+      // second call then serves the lane's two bins only.  The generic body keeps two three-slot calls.
       float lmagn[NS3];
-      log_f32_via_tab_n<NS3>(magn, lmagn, logts);
+      [[maybe_unused]] float lt1_tail = 0.f;
+      if constexpr (STEADY) {
+        load_snr_tails();
+        snr_tail(quant[2]);
+        const float xs[NS3] = {magn[0], magn[1], lane == 1 ? 1.f + 2.f * snrLocPrior[2] : magn[2]};
+        log_f32_via_tab_n<NS3>(xs, lmagn, logts);
+        lt1_tail = lane_bcast(lmagn[2], 1);
+        lmagn[2] = lane_bcast(lmagn[2], 0);
+      } else {
+        log_f32_via_tab_n<NS3>(magn, lmagn, logts);
+      }
+      LOADT(avgPause, V_AVGPAUSE)
 
       NS_STAMP(3)
       // the four cross-bin sums that need only this frame's spectrum and the loaded rows, reduced side by
@@ -634,6 +737,8 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       }
 
       NS_STAMP(4)
+      // (generic body: the row tails ComputeSnr wants, phase 6, requested here: the trackers' work covers the LDS round trip)
+      if constexpr (!STEADY) load_snr_tails();
       // ---- NoiseEstimation (ns_core.c:217-285)
       if (updates < NS_END_STARTUP_LONG) updates++;
       bool quant_new = false;
@@ -697,7 +802,13 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       float whiteNoiseLevel = SC_F(S_WHITE);
       float pinkNoiseNumerator = SC_F(S_PINKNUM);
       float pinkNoiseExp = SC_F(S_PINKEXP);
-      float fd5 = SC_F(S_FD5);
+      float fd5, fd6;
+      {
+        static_assert(S_FD6 == S_FD5 + 1, "read as a pair");
+        float t2[2];
+        srow.template ld<S_FD5, 2>(sv, t2);
+        fd5 = t2[0]; fd6 = t2[1];
+      }
       const bool startup = blockInd < NS_END_STARTUP_SHORT;
       if (startup) {
         const int binA_c = ns_cold(binA);
@@ -713,7 +824,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         const float sum_log_magn = SUM3(lm3);
         const float sum_log_i_log_magn = SUM3(lilm);
         const NsPinkFit fit = ns_pink_fit<kBins>(Tc, whiteNoiseLevel, pinkNoiseNumerator, pinkNoiseExp, sumMagn,
-                                                 overdrive, sum_log_magn, sum_log_i_log_magn, blockInd);
+                                                 SC_F(S_OVERDRIVE), sum_log_magn, sum_log_i_log_magn, blockInd);
         whiteNoiseLevel = fit.whiteNoiseLevel;
         pinkNoiseNumerator = fit.pinkNoiseNumerator;
         pinkNoiseExp = fit.pinkNoiseExp;
@@ -749,29 +860,29 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
 
       NS_STAMP(6)
       // ---- ComputeSnr (ns_core.c:566-588)
-      float snrLocPost[NS3], snrLocPrior[NS3];
       {
-        float dn1[NS3], dn2[NS3], q1[NS3], q2[NS3];
+        const f32x2 eps = {0.0001f, 0.0001f};
+        const f32x2 ns2 = {noise[0], noise[1]}, mg2 = {magn[0], magn[1]};
+        const f32x2 q1 = fdiv2(f32x2{magnPrevA[0], magnPrevA[1]}, f32x2{noisePrev[0], noisePrev[1]} + eps);
+        const f32x2 q2 = fdiv2(mg2, ns2 + eps);  // used where magn > noise
 #pragma unroll
-        for (int k = 0; k < NS3; ++k) {
-          dn1[k] = noisePrev[k] + 0.0001f;
-          dn2[k] = noise[k] + 0.0001f;
-        }
-        fdiv3(magnPrevA, dn1, q1);
-        fdiv3(magn, dn2, q2);  // used where magn > noise
-#pragma unroll
-        for (int k = 0; k < NS3; ++k) {
+        for (int k = 0; k < 2; ++k) {
           const float previousEstimateStsa = q1[k] * smooth[k];
           prevStsa[k] = previousEstimateStsa;
           snrLocPost[k] = 0.f;
           if (magn[k] > noise[k]) snrLocPost[k] = q2[k] - 1.f;
           snrLocPrior[k] = NS_DD_PR_SNR * previousEstimateStsa + (1.f - NS_DD_PR_SNR) * snrLocPost[k];
         }
+        if constexpr (!STEADY) snr_tail(noise[2]);
       }
 
       NS_STAMP(7)
       // ---- ComputeSpectralFlatness (ns_core.c:523-556)
-      float fd0 = SC_F(S_FD0), fd4 = SC_F(S_FD4), fd6 = SC_F(S_FD6);
+      // (featureData[0], [3] and [4] are read from the scalar row in front of their first use)
+      static_assert(S_PMP5 == S_PMP4 + 1 && S_PMP1 == S_PMP0 + 1 && S_PMP2 == S_PMP0 + 2 && S_PMP3 == S_PMP0 + 3,
+                    "scalars read as groups");
+      PriorModel pm;
+      float fd4 = SC_F(S_FD4);
       // (its exponential is evaluated beside bin 128's of exp(-logLrt), each on a lane of one call, once logLrt is
       // updated: the feature is finished there, in front of its first readers, the histogram and the tanh)
       const NsFlatArgs flat = ns_flatness_args<kBins>(flatNum, sumMagn, lane_bcast(magn[0], 0));
@@ -804,9 +915,18 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       // ---- SpeechNoiseProb (ns_core.c:642-749): the likelihood-ratio update
       {
         float t1[NS3], lt1[NS3];
+        LOADT(logLrt, V_LOGLRT)
 #pragma unroll
         for (int k = 0; k < NS3; ++k) t1[k] = 1.f + 2.f * snrLocPrior[k];
-        log_f32_via_tab_n<NS3>(t1, lt1, logts);
+        if constexpr (STEADY) {
+          const float t1p[2] = {t1[0], t1[1]};
+          float lt1p[2];
+          log_f32_via_tab_n<2>(t1p, lt1p, logts);
+          lt1[0] = lt1p[0]; lt1[1] = lt1p[1];
+          lt1[2] = lt1_tail;
+        } else {
+          log_f32_via_tab_n<NS3>(t1, lt1, logts);
+        }
         float tn[NS3], td3[NS3], t2v[NS3];
 #pragma unroll
         for (int k = 0; k < NS3; ++k) {
@@ -825,7 +945,15 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       logLrtTimeAvgKsum = DIV129(logLrtTimeAvgKsum);
       // exp(-logLrt) of the lane's two bins, and two independent wave-uniform exponentials in the third slot of the
       // same call: the flatness feature's on lane 0, bin 128's on every other lane (read back from lane 1)
-      float ev[NS3];
+      // (the scalars of the prior-model map, phase 9, are requested in front of the exponentials, whose table reads wait
+      // anyway: featureData[0] and [3] -- the previous frame's average LRT, for the histogram -- and the model's first four)
+      float ev[NS3], fd0 = SC_F(S_FD0), fd3 = SC_F(S_FD3), pmp2;
+      {
+        float t4[4];
+        srow.template ld<S_PMP0, 4>(sv, t4);
+        pm.p0 = t4[0]; pm.p1 = t4[1]; pmp2 = t4[2]; pm.p3 = t4[3];
+        pm.p4 = pm.p5 = pm.p6 = 0.f;  // (the three weights: read in front of the tanh, unless the window closes here and sets them)
+      }
       {
         float nl[NS3];
 #pragma unroll
@@ -839,15 +967,6 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       NS_STAMP(9)
       // ---- histograms / prior model (FeatureUpdate, ns_core.c:766-790): the new flatness and difference features, the
       // previous frame's average LRT
-      float fd3 = SC_F(S_FD3);  // previous frame's average LRT feeds the histogram
-      PriorModel pm;
-      pm.p0 = SC_F(S_PMP0);
-      pm.p1 = SC_F(S_PMP1);
-      pm.p3 = SC_F(S_PMP3);
-      pm.p4 = SC_F(S_PMP4);
-      pm.p5 = SC_F(S_PMP5);
-      pm.p6 = SC_F(S_PMP6);
-      const float pmp2 = SC_F(S_PMP2);
       int mup0 = updateParsFlag, mup3 = ss.mup3;
       const int mup1 = SC_I(S_MUP1);
       bool window_closed = false;
@@ -880,6 +999,13 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       }
       fd3 = logLrtTimeAvgKsum;
       {
+        if (!window_closed) {
+          float t2[2];
+          srow.template ld<S_PMP4, 2>(sv, t2);
+          pm.p4 = t2[0]; pm.p5 = t2[1];
+          pm.p6 = SC_F(S_PMP6);
+        }
+        priorSpeechProb = SC_F(S_PRIORSPEECHPROB);
         const float widthPrior0 = NS_WIDTH_PR_MAP, widthPrior1 = 2.f * NS_WIDTH_PR_MAP,
                     widthPrior2 = 2.f * NS_WIDTH_PR_MAP;
         const int sgnMap = (int)pmp2;
@@ -949,8 +1075,8 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
           sel3(lt3(ps, F3(NS_PROB_RANGE)), ap + NS_GAMMA_PAUSE * (mg - ap), ap).store(avgPause);
         }
       }
-      STORE3(V_LOGLRT, logLrt) STORE3(V_AVGPAUSE, avgPause)
-      STORE3(V_MAGNPREV_A, magn)  // ns_core.c:1180 (== magnPrevProcess while paired)
+      STORE3_HOT(V_LOGLRT, logLrt) STORE3_HOT(V_AVGPAUSE, avgPause)
+      STORE3_HOT(V_MAGNPREV_A, magn)  // ns_core.c:1180 (== magnPrevProcess while paired)
 
       NS_STAMP(11)
       // ---- Process: decision-directed Wiener gain (ns_core.c:985-1007, 1276-1307)
@@ -977,6 +1103,13 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
           for (int k = 0; k < NS3; ++k) initMagn[k] += magn[k];
           STORE3(V_INITMAGN, initMagn)
         }
+      }
+      float overdrive, denoiseBound;
+      {
+        static_assert(S_DENOISEBOUND == S_OVERDRIVE + 1, "scalars read as a pair");
+        float t2[2];
+        srow.template ld<S_OVERDRIVE, 2>(sv, t2);
+        overdrive = t2[0]; denoiseBound = t2[1];
       }
       float gainv[NS3];
       float gq1[NS3], gq2[NS3], snrP[NS3];
@@ -1011,8 +1144,44 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         re[k] *= gg;
         im[k] *= gg;
       }
-      STORE3(V_SMOOTH, gainv)      // ns_core.c:1304
-      STORE3(V_NOISEPREV, noise)   // ns_core.c:1310
+      STORE3_HOT(V_SMOOTH, gainv)      // ns_core.c:1304
+      STORE3_HOT(V_NOISEPREV, noise)   // ns_core.c:1310
+      // ---- commit the float scalars: every one is final here.  The hand-off build stores them to the image now, on
+      // lane 0 alone, with the bin-128 members of the five rows above; the plain build merges them into `sv` at the
+      // step's end, where it always did
+      auto commit_floats = [&]() __attribute__((always_inline)) {
+        if constexpr (ROW_IMG) {
+          SC_SET_F(S_TAIL0 + V_LOGLRT, logLrt[2]);
+          SC_SET_F(S_TAIL0 + V_AVGPAUSE, avgPause[2]);
+          SC_SET_F(S_TAIL0 + V_MAGNPREV_A, magn[2]);
+          SC_SET_F(S_TAIL0 + V_SMOOTH, gainv[2]);
+          SC_SET_F(S_TAIL0 + V_NOISEPREV, noise[2]);
+        }
+        SC_SET_F(S_SIGNALENERGY, signalEnergy);
+        SC_SET_F(S_SUMMAGN, sumMagn);
+        if (startup) {
+          SC_SET_F(S_WHITE, whiteNoiseLevel);
+          SC_SET_F(S_PINKNUM, pinkNoiseNumerator);
+          SC_SET_F(S_PINKEXP, pinkNoiseExp);
+        }
+        if (window_closed) {
+          SC_SET_F(S_PMP0, pm.p0);
+          SC_SET_F(S_PMP1, pm.p1);
+          SC_SET_F(S_PMP3, pm.p3);
+          SC_SET_F(S_PMP4, pm.p4);
+          SC_SET_F(S_PMP5, pm.p5);
+          SC_SET_F(S_PMP6, pm.p6);
+        }
+        SC_SET_F(S_FD0, fd0);
+        SC_SET_F(S_FD3, fd3);
+        SC_SET_F(S_FD4, fd4);
+        SC_SET_F(S_FD5, fd5);
+        SC_SET_F(S_FD6, fd6);
+        SC_SET_F(S_PRIORSPEECHPROB, priorSpeechProb);
+      };
+      if constexpr (ROW_IMG) {
+        if (lane == 0) commit_floats();
+      }
 
       NS_STAMP(12)
       NS_NEXT_FRAME()
@@ -1077,34 +1246,18 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
 
       NS_STAMP(14)
       // ---- commit scalars
-      SC_SET_I(S_UPDATES, updates);
-      SC_SET_I(S_COUNTER0, counter[0]);
-      SC_SET_I(S_COUNTER1, counter[1]);
-      SC_SET_I(S_COUNTER2, counter[2]);
-      SC_SET_I(S_MUP0, mup0);
-      SC_SET_I(S_MUP3, mup3);
-      SC_SET_F(S_SIGNALENERGY, signalEnergy);
-      SC_SET_F(S_SUMMAGN, sumMagn);
-      if (startup) {
-        SC_SET_F(S_WHITE, whiteNoiseLevel);
-        SC_SET_F(S_PINKNUM, pinkNoiseNumerator);
-        SC_SET_F(S_PINKEXP, pinkNoiseExp);
+      if constexpr (STEADY) {
+        sv = addlanes_bits<(1ull << S_BLOCKIND) | (7ull << S_COUNTER0), 1ull << S_MUP3>(sv);
+      } else {
+        SC_SET_I(S_UPDATES, updates);
+        SC_SET_I(S_COUNTER0, counter[0]);
+        SC_SET_I(S_COUNTER1, counter[1]);
+        SC_SET_I(S_COUNTER2, counter[2]);
+        SC_SET_I(S_MUP0, mup0);
+        SC_SET_I(S_MUP3, mup3);
+        SC_SET_I(S_BLOCKIND, blockInd);
       }
-      if (window_closed) {
-        SC_SET_F(S_PMP0, pm.p0);
-        SC_SET_F(S_PMP1, pm.p1);
-        SC_SET_F(S_PMP3, pm.p3);
-        SC_SET_F(S_PMP4, pm.p4);
-        SC_SET_F(S_PMP5, pm.p5);
-        SC_SET_F(S_PMP6, pm.p6);
-      }
-      SC_SET_F(S_FD0, fd0);
-      SC_SET_F(S_FD3, fd3);
-      SC_SET_F(S_FD4, fd4);
-      SC_SET_F(S_FD5, fd5);
-      SC_SET_F(S_FD6, fd6);
-      SC_SET_I(S_BLOCKIND, blockInd);
-      SC_SET_F(S_PRIORSPEECHPROB, priorSpeechProb);
+      if constexpr (!ROW_IMG) commit_floats();
     };  // step_rest
     if (__builtin_expect(step_steady, 1)) step_rest(std::true_type{});
     else step_rest(std::false_type{});
@@ -1125,6 +1278,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
 #undef LOADV
 #undef LOADT
 #undef STORE3
+#undef STORE3_HOT
 #undef SUM3
 }
 

@@ -224,6 +224,15 @@ __device__ __forceinline__ float mergelanes_vgpr(float row, float val) {
   asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(row) : "v"(val), "s"(mask));
   return row;
 }
+// Integer words of the scalar row stepped in place: the lanes of UP + 1, the lanes of DOWN - 1, the others unchanged.
+// The lane mask goes in as the carry (borrow) of an add (subtract) of 0: two instructions, no per-lane constant held.
+template <unsigned long long UP, unsigned long long DOWN>
+__device__ __forceinline__ float addlanes_bits(float row) {
+  int r = __float_as_int(row);
+  const unsigned long long up = UP, down = DOWN;
+  asm("v_addc_co_u32_e64 %0, vcc, 0, %0, %1\n\tv_subb_co_u32_e64 %0, vcc, %0, 0, %2" : "+v"(r) : "s"(up), "s"(down) : "vcc");
+  return __int_as_float(r);
+}
 // Three wave-uniform words as a per-lane vector: lane K holds a, lane K + 1 b, every other lane c (so lane K + 2 too).
 template <int K>
 __device__ __forceinline__ int lanes3_bits(int a, int b, int c) {

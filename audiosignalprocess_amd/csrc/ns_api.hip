@@ -51,6 +51,8 @@ hipError_t launch_ns_set_policy(float* state, int num_streams, int mode, float o
                                 float denoiseBound, int gainmap, hipStream_t s);
 hipError_t launch_rdft256(float* data, int count, int isgn, const NsTables* T, hipStream_t s, int n = 256);
 hipError_t launch_debug_eval(int fn, float* data, size_t n, const NsTables* T, hipStream_t s);
+hipError_t launch_debug_tanh_wave(unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits,
+                                  const NsTables* T, hipStream_t s);
 hipError_t launch_debug_compare(int fn_a, int fn_b, unsigned start, unsigned count,
                                 unsigned* n_bad, unsigned* bad_bits, float param,
                                 const NsTables* T, hipStream_t s);
@@ -353,6 +355,13 @@ void build_tables(NsTables* T) {
       T->spl[lane][t][1] = wki;
     }
   build_tables_8k(T);
+  // the trackers' counter terms: plain IEEE float division, which is what the kernels' fdiv(1.f, x) returns
+  for (int n = 0; n < kCntTerms; ++n) {
+    T->cnt_terms[n][0] = (float)n;
+    T->cnt_terms[n][1] = (float)(n + 1);
+    T->cnt_terms[n][2] = 1.0f / (float)(n + 1);
+    T->cnt_terms[n][3] = 0.f;
+  }
 }
 
 constexpr int kMaxDevices = 64;
@@ -1665,7 +1674,10 @@ int AspNs_debug_compare(int fn_a, int fn_b, uint32_t start, uint32_t count, uint
   unsigned* d = nullptr;
   HIP_TRY(hipMalloc((void**)&d, 65 * sizeof(unsigned)));
   hipError_t e = hipMemset(d, 0, 65 * sizeof(unsigned));
-  if (e == hipSuccess) e = launch_debug_compare(fn_a, fn_b, start, count, d, d + 1, param, T, nullptr);
+  if (e == hipSuccess && fn_a == 23 && fn_b != 3) e = hipErrorInvalidValue;  // (fn 23 exists beside fn 3 only)
+  if (e == hipSuccess)
+    e = fn_a == 23 ? launch_debug_tanh_wave(start, count, d, d + 1, T, nullptr)
+                   : launch_debug_compare(fn_a, fn_b, start, count, d, d + 1, param, T, nullptr);
   unsigned h[65];
   if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
   (void)hipFree(d);

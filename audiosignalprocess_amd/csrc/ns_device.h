@@ -392,6 +392,44 @@ __device__ __forceinline__ float tanh_f32_via_f64(float a, const double* __restr
   return r;
 }
 
+// The same value -- identical to (float)tanh((double)a) for every float -- with the fp64 work a call of the frame step
+// does not need taken out of the straight line (ns_kernels1.hip: the prior map's three arguments on lanes 0..2 of one
+// call, every other lane repeating lane 2's):
+//   the series is evaluated only where SOME lane of the wave has |a| < 2^-5 (a wave-level branch, rarely taken: a
+//   feature within 2^-7 of its threshold), and selected per lane as above;
+//   the float reciprocal of den = 1 + u is refined ONCE.  den is in (1, 2]: its rounding to float and v_rcp_f32's one
+//   ulp leave the seed within 1.5 x 2^-23 = 2^-22.4 of 1 / den; one Newton step squares that, to 2^-44.8 (the two fma
+//   roundings add 2^-53).  The quotient num * rc = Q (1 + d), |d| <= 2^-44.8; its residual num - qv den = -num d is
+//   exact up to one rounding of a value 2^-44 of num, and the correction takes qv to Q (1 - d e), e the
+//   reciprocal's 2^-44.8: 2^-89 beside the final fma's own rounding, 2^-53 -- what the twice-refined form leaves too.
+//   exp_lean_f64's 2^-51 dominates either way, far inside the 2^-44 that f64_rounds_safely_to_f32 sends to libm.
+// Checked against the libm form for every float bit pattern on the device (tests/test_ns_tanh_wave_gpu.py).
+__device__ __forceinline__ float tanh_f32_via_f64_wave(float a, const double* __restrict__ t64) {
+  const float ax = fabsf(a);
+  const bool finite_ok = ax <= 40.0f;  // beyond: |tanh| rounds to 1, left to libm; NaN too
+  const double u = exp_lean_f64(finite_ok ? -2.0f * ax : 0.0f, t64);
+  const double num = 1.0 - u, den = 1.0 + u;
+  double rc = (double)__builtin_amdgcn_rcpf((float)den);
+  rc = __builtin_fma(__builtin_fma(-den, rc, 1.0), rc, rc);
+  double t = num * rc;
+  t = __builtin_fma(__builtin_fma(-t, den, num), rc, t);
+  const bool small = ax < 0.03125f;
+  if (ASP_NS_RARE(__builtin_amdgcn_ballot_w64(small) != 0)) {
+    const double ad = (double)ax;
+    const double a2 = ad * ad;
+    double sr = 0x1.664f4882c10fap-6;                 // 62/2835
+    sr = __builtin_fma(sr, a2, -0x1.ba1ba1ba1ba1cp-5);  // -17/315
+    sr = __builtin_fma(sr, a2, 0x1.1111111111111p-3);   // 2/15
+    sr = __builtin_fma(sr, a2, -0x1.5555555555555p-2);  // -1/3
+    const double t_small = __builtin_fma(ad * a2, sr, ad);
+    t = small ? t_small : t;
+  }
+  const bool ok = finite_ok && f64_rounds_safely_to_f32(t);
+  float r = __builtin_copysignf((float)t, a);
+  if (ASP_NS_RARE(!ok)) r = (float)tanh((double)a);
+  return r;
+}
+
 // Correctly rounded sqrtf for x >= 0 (Newton on v_rsq with exact residuals).
 // The residual arithmetic underflows below about 2^-102, so inputs under
 // 2^-100 (never produced by int16-range audio) take the generic sqrtf; with

@@ -563,6 +563,17 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
     return;                                                                                    \
   }
 
+  // ---- carried across the steps of a walk (hand-off build).  ComputeSnr and the Wiener gain of step t + 1 both want
+  // magnPrev / (noisePrev + 0.0001f) * smooth (ns_core.c:576-577, 993-994), and step t had exactly that quotient in
+  // registers: its phase 11 forms gq1 = magn / (noise + 0.0001f) and then stores that magn, noise and gain as the three
+  // rows (ns_core.c:1304-1310).  Same operands, same operations, same bits: prevStsa(t + 1) == gq1(t) * gainv(t).  The
+  // step that produced the product owns it; carry_ok says that one did in THIS walk (wave-uniform, tested with a scalar
+  // branch).  A walk starts without it and reads the rows, whoever wrote them last -- the previous walk, the host,
+  // InitStream, an import; the zero-energy exit touches neither the rows nor the carry (ns_core.c:1239-1264).
+  constexpr bool CARRY = FLOW;
+  [[maybe_unused]] f32x2 carry_stsa = {0.f, 0.f};  // the lane's two bins
+  [[maybe_unused]] float carry_stsa_tail = 0.f;    // bin 128
+  [[maybe_unused]] bool carry_ok = false;
   for (;;) {  // the steps of the chunk (one pass in the plain build); no barrier inside: each wave owns its LDS tile
     NS_BUDGET_BACK(0)
     // state rows are requested in two groups, just ahead of their use (requesting all of them before
@@ -624,8 +635,11 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
 
     NS_STAMP(2)
     // second group of state rows (latency hides under magnitude / log / trackers)
-    LOADV(magnPrevA, V_MAGNPREV_A) LOADV(logLrt, V_LOGLRT) LOADV(avgPause, V_AVGPAUSE)
-    LOADV(smooth, V_SMOOTH) LOADV(noisePrev, V_NOISEPREV)
+    // (the hand-off build reads magnPrev and smooth in phase 6, and only in a step that has no carried product)
+    if constexpr (!CARRY) LOADV(magnPrevA, V_MAGNPREV_A)
+    LOADV(logLrt, V_LOGLRT) LOADV(avgPause, V_AVGPAUSE)
+    if constexpr (!CARRY) LOADV(smooth, V_SMOOTH)
+    LOADV(noisePrev, V_NOISEPREV)
     // (their bin-128 members are read from the scalar row where they are first used: wave-uniform values that the
     // hand-off build holds in vector registers, which the transform's end has none to spare of)
 
@@ -661,6 +675,24 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
     ss.mup3 = SC_I(S_MUP3);
     ss.gainmap = SC_I(S_GAINMAP);
     const bool step_steady = steady_on != 0 && ns_step_is_steady(ss);
+    // the trackers' counter terms {n - 1, n, 1 / n} as floats (n - 1 = counter[s] = 0 .. 200): functions of an integer in
+    // a scalar register, read from NsTables::cnt_terms with wave-uniform scalar loads and used in phase 4.  Each body
+    // requests them as its first act -- the earliest place behind the counters; requested in front of the split into the
+    // two bodies, every ns_frame1 kernel spilled vector registers (profiles/README.md).  One dword per load: the
+    // compiler turns a wider read of an entry into a vector load.  (A valid state keeps its counters in 0 .. 200,
+    // ns_core.c:262-272; the index is held inside the table whatever an imported state carries.)
+    static_assert(kCntTerms == NS_END_STARTUP_LONG + 1, "one entry per counter value");
+    float cterm[3][3];
+    auto load_cterms = [&]() __attribute__((always_inline)) {
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        typedef const __attribute__((address_space(4))) float cfloat_k;
+        const unsigned n = (unsigned)ss.counter[s] < (unsigned)NS_END_STARTUP_LONG ? (unsigned)ss.counter[s]
+                                                                                   : (unsigned)NS_END_STARTUP_LONG;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) cterm[s][j] = *(cfloat_k*)(&T->cnt_terms[n][j]);
+      }
+    };
     // ---- the rest of the step, up to the commit of its scalars: ONE text, instantiated as the steady body
     // (steady_c = std::true_type: under the assumes of ns_assume_steady) and as the generic one.  It is a lambda: a
     // `return` inside would leave the lambda and not the kernel, and `continue` is not available; the step ends
@@ -670,6 +702,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       [[maybe_unused]] constexpr int ns_body_tag = STEADY ? 1 : 2;
       if constexpr (STEADY) ns_assume_steady(ss);
       if constexpr (DIAG) diag_steps += STEADY ? 1u : 0x10000u;
+      load_cterms();
       const int blockInd = ss.blockInd;
       float priorSpeechProb;  // (read in front of the tanh of phase 9; overdrive and denoiseBound: phase 11)
       const int gainmap = ss.gainmap;
@@ -683,9 +716,14 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       // the per-bin loop.  noise2: bin 128 of the noise estimate.
       float snrLocPost[NS3], snrLocPrior[NS3];
       auto snr_tail = [&](float noise2) __attribute__((always_inline)) {
-        const float q1t = fdiv(magnPrevA[2], noisePrev[2] + 0.0001f);
         const float q2t = fdiv(magn[2], noise2 + 0.0001f);  // used where magn > noise
-        const float previousEstimateStsa = q1t * smooth[2];
+        float previousEstimateStsa;
+        if (CARRY && carry_ok) {
+          previousEstimateStsa = carry_stsa_tail;
+        } else {
+          const float q1t = fdiv(magnPrevA[2], noisePrev[2] + 0.0001f);
+          previousEstimateStsa = q1t * smooth[2];
+        }
         prevStsa[2] = previousEstimateStsa;
         snrLocPost[2] = 0.f;
         if (magn[2] > noise2) snrLocPost[2] = q2t - 1.f;
@@ -744,27 +782,25 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       bool quant_new = false;
       // Bin 128 of the three trackers: three independent chains with one formula, evaluated ONCE with tracker s on
       // lane 48 + s -- where its lquantile tail already sits in the scalar row; its density tail, three lanes up in
-      // the same DPP row, comes down by one row shift, and n - 1 / n / 1 / n are built per lane from the three
-      // counters.  Every value goes through the operations of its own wave-uniform pass; the other lanes compute
-      // on whatever the row holds and are dropped by the masked merge.
+      // the same DPP row, comes down by one row shift, and n - 1 / n / 1 / n are put on the three lanes from the
+      // trackers' table terms (cterm).  Every value goes through the operations of its own wave-uniform pass; the
+      // other lanes compute on whatever the row holds and are dropped by the masked merge.
       constexpr int kLqLane = S_TAIL0 + V_LQ0, kDenLane = S_TAIL0 + V_DEN0;
       static_assert(V_LQ1 == V_LQ0 + 1 && V_LQ2 == V_LQ0 + 2 && V_DEN1 == V_DEN0 + 1 && V_DEN2 == V_DEN0 + 2 &&
                     kDenLane == kLqLane + 3 && kLqLane / 16 == (kDenLane + 2) / 16,
                     "the tracker tails: three + three consecutive lanes of one DPP row");
       float lqT = sv, denT = dpp_move<0x103>(sv);  // row_shl:3: lane L reads lane L + 3
-      float rcnt1v;
       {
-        const int cntb = lanes3_bits<kLqLane>(counter[0], counter[1], counter[2]);
-        const float cntv = (float)cntb, cnt1v = (float)(cntb + 1);
-        rcnt1v = fdiv(1.f, cnt1v);  // == 1.f / cnt1 (cnt1 = 1 .. 201)
+#define NS_LANES3_F(j) __int_as_float(lanes3_bits<kLqLane>(__float_as_int(cterm[0][j]), __float_as_int(cterm[1][j]), \
+                                                           __float_as_int(cterm[2][j])))
+        const float cntv = NS_LANES3_F(0), cnt1v = NS_LANES3_F(1), rcnt1v = NS_LANES3_F(2);  // rcnt1 == 1.f / cnt1
+#undef NS_LANES3_F
         tracker_step1(lqT, denT, lmagn[2], cntv, cnt1v, rcnt1v);
       }
 #pragma unroll
       for (int s = 0; s < 3; ++s) {
         {
-          const float cnt = (float)counter[s];
-          const float cnt1 = (float)(counter[s] + 1);
-          const float rcnt1 = lane_bcast(rcnt1v, kLqLane + s);
+          const float cnt = cterm[s][0], cnt1 = cterm[s][1], rcnt1 = cterm[s][2];
           f32x2 lq = {LQ[s][0], LQ[s][1]}, den = {DEN[s][0], DEN[s][1]};
           tracker_step2(lq, den, f32x2{lmagn[0], lmagn[1]}, cnt, cnt1, rcnt1);
           LQ[s][0] = lq.x; LQ[s][1] = lq.y;
@@ -863,11 +899,18 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       {
         const f32x2 eps = {0.0001f, 0.0001f};
         const f32x2 ns2 = {noise[0], noise[1]}, mg2 = {magn[0], magn[1]};
-        const f32x2 q1 = fdiv2(f32x2{magnPrevA[0], magnPrevA[1]}, f32x2{noisePrev[0], noisePrev[1]} + eps);
+        f32x2 stsa2;
+        if (CARRY && carry_ok) {
+          stsa2 = carry_stsa;
+        } else {
+          if constexpr (CARRY) { LOADV(magnPrevA, V_MAGNPREV_A) LOADV(smooth, V_SMOOTH) }
+          const f32x2 q1 = fdiv2(f32x2{magnPrevA[0], magnPrevA[1]}, f32x2{noisePrev[0], noisePrev[1]} + eps);
+          stsa2 = f32x2{q1[0] * smooth[0], q1[1] * smooth[1]};
+        }
         const f32x2 q2 = fdiv2(mg2, ns2 + eps);  // used where magn > noise
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-          const float previousEstimateStsa = q1[k] * smooth[k];
+          const float previousEstimateStsa = stsa2[k];
           prevStsa[k] = previousEstimateStsa;
           snrLocPost[k] = 0.f;
           if (magn[k] > noise[k]) snrLocPost[k] = q2[k] - 1.f;
@@ -1021,7 +1064,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         const float arg2 = widthPrior * (fd4 - pm.p3);
         // the three tanh() of :696-725 evaluated on lanes 0..2 of one call
         const float arg = lane == 0 ? arg0 : (lane == 1 ? arg1 : arg2);
-        const float th = tanh_f32_via_f64(arg, exp2s);
+        const float th = tanh_f32_via_f64_wave(arg, exp2s);
         priorSpeechProb = ns_prior_update(priorSpeechProb, pm, ns_prior_indicator(lane_bcast(th, 0)),
                                           ns_prior_indicator(lane_bcast(th, 1)), ns_prior_indicator(lane_bcast(th, 2)));
       }
@@ -1143,6 +1186,11 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         gainv[k] = gg;
         re[k] *= gg;
         im[k] *= gg;
+      }
+      if constexpr (CARRY) {  // the next step's previous-frame estimate, from the values the three rows are stored from
+        carry_stsa = f32x2{gq1[0], gq1[1]} * f32x2{gainv[0], gainv[1]};
+        carry_stsa_tail = gq1[2] * gainv[2];
+        carry_ok = true;
       }
       STORE3_HOT(V_SMOOTH, gainv)      // ns_core.c:1304
       STORE3_HOT(V_NOISEPREV, noise)   // ns_core.c:1310
@@ -1305,9 +1353,30 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_diag_kernel(float* __restric
   ns_frame1_run<false, FLOW, true>(state, hist_all, T, in, out, num_streams, steady_on, fa, dg);
 }
 
+// Test seam: the frame step's tanh (tanh_f32_via_f64_wave, which only this file uses) against (float)tanh((double)x) on
+// every float whose bit pattern is in [start, start + count); the protocol of ns_kernels.hip's debug_compare_kernel.
+__global__ void debug_tanh_wave_kernel(unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits,
+                                       const NsTables* __restrict__ T) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const float x = __uint_as_float(start + i);
+  const float a = tanh_f32_via_f64_wave(x, T->exp2_64), b = (float)tanh((double)x);
+  const bool same = (__float_as_uint(a) == __float_as_uint(b)) || (a != a && b != b);
+  if (!same) {
+    const unsigned k = atomicAdd(n_bad, 1u);
+    if (k < 64) bad_bits[k] = start + i;
+  }
+}
+
 }  // namespace
 
 namespace aspns {
+
+hipError_t launch_debug_tanh_wave(unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits,
+                                  const NsTables* T, hipStream_t s) {
+  hipLaunchKernelGGL(debug_tanh_wave_kernel, dim3((count + 255u) / 256u), dim3(256), 0, s, start, count, n_bad, bad_bits, T);
+  return hipGetLastError();
+}
 
 // stamps / step_counts: diagnostics; either one selects the diagnostic kernel (float frames only)
 hipError_t launch_ns_frame1(bool io16, float* state, int32_t* hist, const NsTables* T,

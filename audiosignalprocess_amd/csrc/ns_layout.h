@@ -82,6 +82,8 @@ constexpr int kStreamDwords = (kStreamDwordsRaw + 63) / 64 * 64;  // 256-byte mu
 constexpr int kHistStride = 1024;
 constexpr int kHistDwords = 3 * kHistStride;
 
+constexpr int kCntTerms = 200 + 1;  // the values a tracker's counter takes: 0 .. END_STARTUP_LONG (ns/defines.h:20)
+
 // Constant tables (one copy per device).
 struct NsTables {
   float window[kAnal];        // kBlocks160w256 (ns/windows_private.h:94-147)
@@ -108,9 +110,14 @@ struct NsTables {
   float sum_log_i8;           // sequential sums over i = 5..64, ns_core.c:1094-1095 with magnLen 65
   float sum_log_i_square8;
   float pad8[2];
+  // the quantile trackers' counter terms (ns_core.c:232-260, counter = n - 1 = 0 .. 200): {(float)(n - 1), (float)n,
+  // 1.0f / (float)n, 0}, one 16-byte entry per counter value, read with wave-uniform scalar loads (ns_kernels1.hip).
+  // Appended behind everything else: nothing that the other kernels stage moves.
+  float cnt_terms[kCntTerms][4];
 };
 
 static_assert(__builtin_offsetof(NsTables, logtab) % 16 == 0, "logtab is read as double2");
+static_assert(__builtin_offsetof(NsTables, cnt_terms) % 16 == 0, "a cnt_terms entry does not straddle a 16-byte line");
 static_assert(__builtin_offsetof(NsTables, spl) == __builtin_offsetof(NsTables, tw2) + sizeof(float) * 3 * 32 * 8,
               "ns_kernels2.hip stages tw2 and spl as one block");
 

@@ -276,7 +276,9 @@ size_t AspNs_host_tables_size(void);
  * (lean fp64 path with libm fallback), 1/2/3 = libm-based (float)log / exp /
  * tanh of (double)x; 4 = x / param, 5 = the kernels' division by a wave-uniform
  * divisor, 6 = the kernels' lean division x / param, 7 = param / x, 8 = lean
- * param / x, 9 = sqrtf, 10 = the kernels' sqrt, 11 / 12 = the kernels' exp / tanh.
+ * param / x, 9 = sqrtf, 10 = the kernels' sqrt, 11 / 12 = the kernels' exp / tanh;
+ * 23 = the pair-layout frame step's form of the tanh (debug_compare only, as fn_a
+ * beside fn_b = 3).
  * debug_eval maps a host array in place; debug_compare
  * evaluates fn_a and fn_b on every float with bit pattern in
  * [start, start+count) and reports how many differ (first 64 patterns). */

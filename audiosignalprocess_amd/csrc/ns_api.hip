@@ -53,6 +53,7 @@ hipError_t launch_rdft256(float* data, int count, int isgn, const NsTables* T, h
 hipError_t launch_debug_eval(int fn, float* data, size_t n, const NsTables* T, hipStream_t s);
 hipError_t launch_debug_tanh_wave(unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits,
                                   const NsTables* T, hipStream_t s);
+hipError_t launch_debug_guards_wave(unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits, hipStream_t s);
 hipError_t launch_debug_compare(int fn_a, int fn_b, unsigned start, unsigned count,
                                 unsigned* n_bad, unsigned* bad_bits, float param,
                                 const NsTables* T, hipStream_t s);
@@ -1675,9 +1676,11 @@ int AspNs_debug_compare(int fn_a, int fn_b, uint32_t start, uint32_t count, uint
   HIP_TRY(hipMalloc((void**)&d, 65 * sizeof(unsigned)));
   hipError_t e = hipMemset(d, 0, 65 * sizeof(unsigned));
   if (e == hipSuccess && fn_a == 23 && fn_b != 3) e = hipErrorInvalidValue;  // (fn 23 exists beside fn 3 only)
+  if (e == hipSuccess && fn_a == 24 && fn_b != 9) e = hipErrorInvalidValue;  // (fn 24: beside sqrtf, fn 9, and sat16p)
   if (e == hipSuccess)
-    e = fn_a == 23 ? launch_debug_tanh_wave(start, count, d, d + 1, T, nullptr)
-                   : launch_debug_compare(fn_a, fn_b, start, count, d, d + 1, param, T, nullptr);
+    e = fn_a == 23   ? launch_debug_tanh_wave(start, count, d, d + 1, T, nullptr)
+        : fn_a == 24 ? launch_debug_guards_wave(start, count, d, d + 1, nullptr)
+                     : launch_debug_compare(fn_a, fn_b, start, count, d, d + 1, param, T, nullptr);
   unsigned h[65];
   if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
   (void)hipFree(d);

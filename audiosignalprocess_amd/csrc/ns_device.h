@@ -123,32 +123,41 @@ __device__ __forceinline__ float div_by_uniform(float a, float d, float rd) {
 // every use below (denominators are x + 1e-4, 1 + x, overdrive + x or a
 // density > 0 with int16-range audio).  Checked against `/` on the device over
 // full mantissa sweeps (tests/test_ns_gpu.py).
-__device__ __forceinline__ float fdiv(float n, float d) {
+// The division is stated in two parts -- the refined reciprocal, which depends on the divisor alone, and the quotient
+// from it -- so that a caller whose divisor stays the same from call to call can keep the first (ns_kernels1.hip);
+// fdiv is the two back to back.
+__device__ __forceinline__ float fdiv_rcp(float d) {
   const float r0 = __builtin_amdgcn_rcpf(d);
   const float e0 = __builtin_fmaf(-d, r0, 1.0f);
-  const float r1 = __builtin_fmaf(e0, r0, r0);
+  return __builtin_fmaf(e0, r0, r0);
+}
+__device__ __forceinline__ float fdiv_quot(float n, float d, float r1) {  // r1 == fdiv_rcp(d)
   const float q0 = n * r1;
   const float e1 = __builtin_fmaf(-d, q0, n);
   const float q1 = __builtin_fmaf(e1, r1, q0);
   const float e2 = __builtin_fmaf(-d, q1, n);
   return __builtin_fmaf(e2, r1, q1);
 }
+__device__ __forceinline__ float fdiv(float n, float d) { return fdiv_quot(n, d, fdiv_rcp(d)); }
 // Two correctly rounded divisions at a time: the same arithmetic as fdiv with the seven
 // multiply-add steps issued as packed-f32 instructions (one issue slot for two quotients).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 fdiv2(f32x2 n, f32x2 d) {
+__device__ __forceinline__ f32x2 fdiv2_rcp(f32x2 d) {
   f32x2 r0;
   r0.x = __builtin_amdgcn_rcpf(d.x);
   r0.y = __builtin_amdgcn_rcpf(d.y);
   const f32x2 one = {1.0f, 1.0f};
   const f32x2 e0 = __builtin_elementwise_fma(-d, r0, one);
-  const f32x2 r1 = __builtin_elementwise_fma(e0, r0, r0);
+  return __builtin_elementwise_fma(e0, r0, r0);
+}
+__device__ __forceinline__ f32x2 fdiv2_quot(f32x2 n, f32x2 d, f32x2 r1) {  // r1 == fdiv2_rcp(d)
   const f32x2 q0 = n * r1;
   const f32x2 e1 = __builtin_elementwise_fma(-d, q0, n);
   const f32x2 q1 = __builtin_elementwise_fma(e1, r1, q0);
   const f32x2 e2 = __builtin_elementwise_fma(-d, q1, n);
   return __builtin_elementwise_fma(e2, r1, q1);
 }
+__device__ __forceinline__ f32x2 fdiv2(f32x2 n, f32x2 d) { return fdiv2_quot(n, d, fdiv2_rcp(d)); }
 // Three bins of a lane of the one-stream-per-wave kernel (two owned + bin 128) as one packed pair
 // and a scalar: +, -, * and fma on an F3 compile to v_pk_* for the pair.  Every operation is the IEEE
 // single operation of its scalar spelling (no contraction), so results are bit-identical to per-bin loops.
@@ -565,6 +574,55 @@ __device__ __forceinline__ void fsqrt_n(const float (&x)[N], float (&out)[N]) {
     for (int k = 0; k < N; ++k)
       if (x[k] < 0x1p-100f && x[k] > 0.0f) out[k] = sqrt_f32_slow(x[k]);
   }
+}
+
+// The same values with the pass-through of +-0 and +inf taken out of the straight line.  For exactly these arguments
+// the Newton result is a NaN (v_rsq gives inf or 0, and x times it is 0 * inf), so ONE compare of each result --
+// "not finite" -- finds them, with the NaN of a NaN or negative argument and the +inf that a negative subnormal gives
+// (its v_rsq is -inf); the masks are OR-ed over the arguments and the wave, and the selects of fsqrt_n run only where
+// SOME lane of the wave holds such a result (a wave-level branch: the frame step of ns_kernels1.hip meets a squared
+// magnitude of exactly zero in no frame of int16-range audio).  A lane that skips them has no such argument in any
+// slot, so its Newton results are what the selects would have kept.  (The compare is on the result and not a class
+// test of the argument because the wave-level mask of a single compare is that compare's scalar result, while the
+// compiler rebuilds the mask of a class test through a select and a second compare.)  Behind the branch, where it is
+// free, a negative argument gets sqrtf's NaN -- fsqrt_n returns +inf for a negative subnormal, outside its contract
+// x >= 0 -- so this form equals sqrtf for EVERY float bit pattern (tests/test_ns_guards_gpu.py sweeps them on the
+// device).  The tiny-argument branch is fsqrt_n's.  fsqrt_n itself stays as it is: ns_kernels.hip and
+// ns_kernels2.hip use it.
+template <int N>
+__device__ __forceinline__ void fsqrt_n_wave(const float (&x)[N], float (&out)[N]) {
+  unsigned bad = 0;
+  unsigned long long passes = 0;  // the wave's lanes with a result that is not finite in some slot
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const float xv = x[k];
+    const float r = __builtin_amdgcn_rsqf(xv);
+    float g = xv * r;
+    float h = 0.5f * r;
+    const float e = __builtin_fmaf(-h, g, 0.5f);
+    g = __builtin_fmaf(g, e, g);
+    h = __builtin_fmaf(h, e, h);
+    const float d = __builtin_fmaf(-g, g, xv);
+    out[k] = __builtin_fmaf(d, h, g);
+    passes |= __builtin_amdgcn_ballot_w64(!(fabsf(out[k]) < __builtin_inff()));
+    bad |= (xv < 0x1p-100f && xv > 0.0f) ? 1u : 0u;
+  }
+  if (ASP_NS_RARE(passes != 0)) {
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+      out[k] = (x[k] == 0.0f || x[k] == __builtin_inff()) ? x[k] : (x[k] < 0.0f ? __builtin_nanf("") : out[k]);
+  }
+  if (ASP_NS_RARE(bad != 0)) {
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+      if (x[k] < 0x1p-100f && x[k] > 0.0f) out[k] = sqrt_f32_slow(x[k]);
+  }
+}
+__device__ __forceinline__ float fsqrt_wave(float x) {
+  const float xs[1] = {x};
+  float out[1];
+  fsqrt_n_wave<1>(xs, out);
+  return out[0];
 }
 
 // ---- lean fp64 forms of the echo canceller's float transcendentals (aec_core.c:280, 487-488) ----

@@ -452,12 +452,10 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
     NS_STAMP(0)
     outj = out + (size_t)flow_slot * fa.per;
     const int lane_c = ns_cold(lane);
-    const float4 ha = sa.ld4(kOffAnaHist, 4 * (lane_c < 24 ? lane_c : 23));
-    const bool hsel = lane_c < 24;
-    s4.x = hsel ? ha.x : s4in.x;
-    s4.y = hsel ? ha.y : s4in.y;
-    s4.z = hsel ? ha.z : s4in.z;
-    s4.w = hsel ? ha.w : s4in.w;
+    // each lane takes its own source, the carried 96 (lanes 0..23) or the new 160, into the same registers: the read of
+    // the carried samples runs on its lanes alone, over what they loaded of the new frame and dropped
+    s4 = s4in;
+    if (lane_c < 24) s4 = sa.ld4(kOffAnaHist, 4 * lane_c);
     const int q2_c = lane_c & 30;  // 2 q
     carryA = sa.ld2(kOffSynt, q2_c + 32 * (lane_c & 1));
     carryB = sa.ld2(kOffSynt, q2_c + 64);
@@ -574,6 +572,15 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
   [[maybe_unused]] f32x2 carry_stsa = {0.f, 0.f};  // the lane's two bins
   [[maybe_unused]] float carry_stsa_tail = 0.f;    // bin 128
   [[maybe_unused]] bool carry_ok = false;
+  // The refined reciprocal of quant + 0.0001f (the first part of ComputeSnr's division, fdiv2_rcp / fdiv_rcp): in the
+  // steady body the noise estimate IS the stored quantile, which only a publish changes, and a publish is a generic
+  // step.  A steady step owns it; rcpq_ok says that the previous live step of THIS walk was one (a generic step clears
+  // it, a walk starts without it, the zero-energy exit touches neither the quantile nor the carry).
+  // (the product kernels only: the diagnostic hand-off kernel has no registers for it, as for ROW_IMG)
+  constexpr bool RCPQ = FLOW && !DIAG;
+  [[maybe_unused]] f32x2 rcpq = {0.f, 0.f};
+  [[maybe_unused]] float rcpq_tail = 0.f;
+  [[maybe_unused]] bool rcpq_ok = false;
   for (;;) {  // the steps of the chunk (one pass in the plain build); no barrier inside: each wave owns its LDS tile
     NS_BUDGET_BACK(0)
     // state rows are requested in two groups, just ahead of their use (requesting all of them before
@@ -653,7 +660,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
     if (lane == 0) im[0] = 0.f;
     {
       float m2[2] = {re[0] * re[0] + im[0] * im[0], re[1] * re[1] + im[1] * im[1]}, rt[2];
-      fsqrt_n<2>(m2, rt);
+      fsqrt_n_wave<2>(m2, rt);
       magn[0] = rt[0] + 1.f;
       magn[1] = rt[1] + 1.f;
     }
@@ -716,7 +723,17 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       // the per-bin loop.  noise2: bin 128 of the noise estimate.
       float snrLocPost[NS3], snrLocPrior[NS3];
       auto snr_tail = [&](float noise2) __attribute__((always_inline)) {
-        const float q2t = fdiv(magn[2], noise2 + 0.0001f);  // used where magn > noise
+        const float d2t = noise2 + 0.0001f;
+        float r2t;
+        if (RCPQ && STEADY && rcpq_ok) {
+          r2t = rcpq_tail;
+        } else {
+          r2t = fdiv_rcp(d2t);
+          // (a marked value: the compiler turns an unmarked short else-path into both paths and a select)
+          if constexpr (RCPQ && STEADY) asm volatile("; the quantile's reciprocal, bin 128" : "+v"(r2t));
+        }
+        if constexpr (RCPQ && STEADY) rcpq_tail = r2t;
+        const float q2t = fdiv_quot(magn[2], d2t, r2t);  // used where magn > noise
         float previousEstimateStsa;
         if (CARRY && carry_ok) {
           previousEstimateStsa = carry_stsa_tail;
@@ -907,7 +924,19 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
           const f32x2 q1 = fdiv2(f32x2{magnPrevA[0], magnPrevA[1]}, f32x2{noisePrev[0], noisePrev[1]} + eps);
           stsa2 = f32x2{q1[0] * smooth[0], q1[1] * smooth[1]};
         }
-        const f32x2 q2 = fdiv2(mg2, ns2 + eps);  // used where magn > noise
+        const f32x2 d2 = ns2 + eps;
+        f32x2 r2;
+        if (RCPQ && STEADY && rcpq_ok) {
+          r2 = rcpq;
+        } else {
+          r2 = fdiv2_rcp(d2);
+          if constexpr (RCPQ && STEADY) asm volatile("; the quantile's reciprocal" : "+v"(r2));
+        }
+        if constexpr (RCPQ) {
+          if constexpr (STEADY) rcpq = r2;
+          rcpq_ok = STEADY;  // (a generic step may publish a quantile or blend the start-up model into the estimate)
+        }
+        const f32x2 q2 = fdiv2_quot(mg2, d2, r2);  // used where magn > noise
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const float previousEstimateStsa = stsa2[k];
@@ -926,6 +955,8 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
                     "scalars read as groups");
       PriorModel pm;
       float fd4 = SC_F(S_FD4);
+      [[maybe_unused]] NsDiffArgs diffa;
+      [[maybe_unused]] float diff_varMagn;
       // (its exponential is evaluated beside bin 128's of exp(-logLrt), each on a lane of one call, once logLrt is
       // updated: the feature is finished there, in front of its first readers, the histogram and the tanh)
       const NsFlatArgs flat = ns_flatness_args<kBins>(flatNum, sumMagn, lane_bcast(magn[0], 0));
@@ -951,7 +982,10 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         varPause = DIV129(varPause);
         varMagn = DIV129(varMagn);
         fd6 += signalEnergy;
-        fd4 = ns_spectral_diff(covMagnPause, varPause, varMagn, fd4, fd5);
+        // (its two quotients are divided in phase 8, each beside another wave-uniform quotient that is independent of
+        // it: the first with bin 128's of the likelihood ratio, the second with the flatness feature's)
+        diffa = ns_spectral_diff_args(covMagnPause, varPause, fd5);
+        diff_varMagn = varMagn;
       }
 
       NS_STAMP(8)
@@ -976,7 +1010,12 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
           tn[k] = 2.f * snrLocPrior[k];
           td3[k] = t1[k] + 0.0001f;
         }
-        fdiv3(tn, td3, t2v);
+        {
+          const f32x2 a = fdiv2(f32x2{tn[0], tn[1]}, f32x2{td3[0], td3[1]});
+          const f32x2 b = fdiv2(f32x2{tn[2], diffa.n1}, f32x2{td3[2], diffa.d1});
+          t2v[0] = a.x; t2v[1] = a.y; t2v[2] = b.x;
+          diffa.n1 = diff_varMagn - b.y;  // avgDiffNormMagn's numerator (ns_core.c:630)
+        }
 #pragma unroll
         for (int k = 0; k < NS3; ++k) {
           const float t2 = t2v[k];
@@ -1003,7 +1042,11 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         for (int k = 0; k < NS3; ++k) nl[k] = -logLrt[k];
         nl[2] = lane == 0 ? flat.arg : nl[2];
         exp_f32_via_f64_n<NS3>(nl, ev, exp2s);
-        fd0 = ns_flatness_update(fd0, lane_bcast(ev[2], 0), flat.den);  // ns_core.c:551-555
+        {
+          const f32x2 qq = fdiv2(f32x2{lane_bcast(ev[2], 0), diffa.n1}, f32x2{flat.den, diffa.d2});
+          fd0 = ns_flatness_update_q(fd0, qq.x);  // ns_core.c:551-555
+          fd4 = ns_spectral_diff_q(fd4, qq.y);    // ns_core.c:631-634
+        }
         ev[2] = lane_bcast(ev[2], 1);
       }
 
@@ -1265,7 +1308,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         e2 += td1 * td1;
         e2 += td2 * td2;
         e2 += td3s * td3s;
-        factor = ns_gain_factor(wave_sum_bcast(e2), energy1, denoiseBound, priorSpeechProb);
+        factor = ns_gain_factor<true>(wave_sum_bcast(e2), energy1, denoiseBound, priorSpeechProb);
       }
 
       // ---- synthesis window, overlap-add, emit 160, carry 96 (ns_core.c:1344-1359)
@@ -1280,16 +1323,29 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         const float cB0 = (g == 0 && h == 0) ? carryB.x : 0.f, cB1 = (g == 0 && h == 0) ? carryB.y : 0.f;
         const float oA0 = cA0 + factor * (wA.x * td0), oA1 = cA1 + factor * (wA.y * td1);
         const float oB0 = cB0 + factor * (wB.x * td2), oB1 = cB1 + factor * (wB.y * td3s);
-        if (nA >= 160) {
-          sa.st2(kOffSynt, nA - 160, oA0, oA1);
-        } else {
-          store2p<IO16>(y, nA, sat16p(oA0), sat16p(oA1));
-        }
-        if (nB >= 160) {
-          sa.st2(kOffSynt, nB - 160, oB0, oB1);
-        } else {
-          store2p<IO16>(y, nB, sat16p(oB0), sat16p(oB1));
-        }
+        // Saturation of the emitted samples (ns_core.c:1352-1356) behind ONE wave-level test: a value with
+        // |x| <= 32767 is what sat16p returns for it, so where no lane holds another the values are stored as they are;
+        // otherwise -- x > 32767, x < -32767, a NaN, on any lane, the synthesis tail's included -- the same stores with
+        // sat16p, out of line.  The tail in LDS is stored unsaturated either way.
+        auto emit = [&](auto sat_c) __attribute__((always_inline)) {
+          constexpr bool SAT = decltype(sat_c)::value;
+          if (nA >= 160) {
+            sa.st2(kOffSynt, nA - 160, oA0, oA1);
+          } else {
+            store2p<IO16>(y, nA, SAT ? sat16p(oA0) : oA0, SAT ? sat16p(oA1) : oA1);
+          }
+          if (nB >= 160) {
+            sa.st2(kOffSynt, nB - 160, oB0, oB1);
+          } else {
+            store2p<IO16>(y, nB, SAT ? sat16p(oB0) : oB0, SAT ? sat16p(oB1) : oB1);
+          }
+        };
+        // (one compare's lane mask per value, OR-ed with scalar instructions)
+        const unsigned long long may_clip =
+            (__builtin_amdgcn_ballot_w64(sat16p_may_clip(oA0)) | __builtin_amdgcn_ballot_w64(sat16p_may_clip(oA1))) |
+            (__builtin_amdgcn_ballot_w64(sat16p_may_clip(oB0)) | __builtin_amdgcn_ballot_w64(sat16p_may_clip(oB1)));
+        if (ASP_NS_RARE(may_clip != 0)) emit(std::true_type{});
+        else emit(std::false_type{});
       }
 
       NS_STAMP(14)
@@ -1368,9 +1424,32 @@ __global__ void debug_tanh_wave_kernel(unsigned start, unsigned count, unsigned*
   }
 }
 
+// Test seam: the frame step's wave-level guards on every float whose bit pattern is in [start, start + count), 64
+// consecutive patterns to a wave -- the emitted sample (stored as it is unless sat16p_may_clip holds on some lane of the
+// wave, through sat16p otherwise) against sat16p, and fsqrt_wave against sqrtf.
+__global__ void debug_guards_wave_kernel(unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const float x = __uint_as_float(start + i);
+  float emitted = x;
+  if (__builtin_amdgcn_ballot_w64(sat16p_may_clip(x)) != 0) emitted = sat16p(x);
+  const float a = fsqrt_wave(x), b = sqrtf(x);
+  const bool same = __float_as_uint(emitted) == __float_as_uint(sat16p(x)) &&
+                    ((__float_as_uint(a) == __float_as_uint(b)) || (a != a && b != b));
+  if (!same) {
+    const unsigned k = atomicAdd(n_bad, 1u);
+    if (k < 64) bad_bits[k] = start + i;
+  }
+}
+
 }  // namespace
 
 namespace aspns {
+
+hipError_t launch_debug_guards_wave(unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits, hipStream_t s) {
+  hipLaunchKernelGGL(debug_guards_wave_kernel, dim3((count + 255u) / 256u), dim3(256), 0, s, start, count, n_bad, bad_bits);
+  return hipGetLastError();
+}
 
 hipError_t launch_debug_tanh_wave(unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits,
                                   const NsTables* T, hipStream_t s) {

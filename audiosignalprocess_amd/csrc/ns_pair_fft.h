@@ -198,6 +198,9 @@ __device__ __forceinline__ void store2p(float* y, int idx, float a, float b) {
 __device__ __forceinline__ float sat16p(float x) {
   return x > 32767 ? 32767 : (x < -32768 ? -32768 : x);
 }
+// false only where sat16p(x) is x itself, bit for bit: |x| <= 32767.  True for x > 32767, for x < -32767 (the band
+// [-32768, -32767) is flagged needlessly) and for a NaN, which sat16p returns as it is.  One compare of |x|.
+__device__ __forceinline__ bool sat16p_may_clip(float x) { return !(fabsf(x) <= 32767.f); }
 
 // v_writelane_b32: the (wave-uniform) value goes into lane K of the scalar row
 template <int K>

@@ -257,20 +257,34 @@ __device__ __forceinline__ NsFlatArgs ns_flatness_args(float sumLogMagn1, float 
   num = ns_div_bins<NB>(num);
   return {num, den};
 }
-__device__ __forceinline__ float ns_flatness_update(float fd0, float expArg, float den) {
-  const float spectralTmp = fdiv(expArg, den);
+// (the _q forms take a quotient the caller has formed: ns_kernels1.hip divides two independent wave-uniform quotients
+// at a time, ns_device.h fdiv2)
+__device__ __forceinline__ float ns_flatness_update_q(float fd0, float spectralTmp) {
   fd0 += NS_SPECT_FL_TAVG * (spectralTmp - fd0);
   return fd0;
+}
+__device__ __forceinline__ float ns_flatness_update(float fd0, float expArg, float den) {
+  return ns_flatness_update_q(fd0, fdiv(expArg, den));
 }
 
 // Spectral difference once its covariance and variances (sums over the bins, divided by their count) are in
 // (ns_core.c:628-634): the time-averaged feature, featureData[4].  fd5: after ns_startup_fd5.
+// Its two quotients are n1 / d1 and (varMagn - n1 / d1) / d2:
+struct NsDiffArgs {
+  float n1, d1, d2;
+};
+__device__ __forceinline__ NsDiffArgs ns_spectral_diff_args(float covMagnPause, float varPause, float fd5) {
+  return {covMagnPause * covMagnPause, varPause + 0.0001f, fd5 + 0.0001f};
+}
+__device__ __forceinline__ float ns_spectral_diff_q(float fd4, float avgDiffNormMagn) {
+  fd4 += NS_SPECT_DIFF_TAVG * (avgDiffNormMagn - fd4);
+  return fd4;
+}
 __device__ __forceinline__ float ns_spectral_diff(float covMagnPause, float varPause, float varMagn, float fd4,
                                                   float fd5) {
   float avgDiffNormMagn = varMagn - fdiv(covMagnPause * covMagnPause, varPause + 0.0001f);
   avgDiffNormMagn = fdiv(avgDiffNormMagn, fd5 + 0.0001f);
-  fd4 += NS_SPECT_DIFF_TAVG * (avgDiffNormMagn - fd4);
-  return fd4;
+  return ns_spectral_diff_q(fd4, avgDiffNormMagn);
 }
 
 // Feature-window bookkeeping behind a close (ns_core.c:773-788): the window reopens with modelUpdatePars[1] frames,
@@ -304,11 +318,13 @@ __device__ __forceinline__ float ns_prior_update(float priorSpeechProb, PriorMod
 }
 
 // Energy-based gain compensation (ns_core.c:1321-1342): the output's scale factor from the frame's energy in front of
-// the filter (energy1) and behind it (energy2).
+// the filter (energy1) and behind it (energy2).  WAVE_SQRT: the square root in its wave-level form (fsqrt_wave).
+template <bool WAVE_SQRT = false>
 __device__ __forceinline__ float ns_gain_factor(float energy2, float energy1, float denoiseBound,
                                                 float priorSpeechProb) {
   float factor1 = 1.f, factor2 = 1.f;
-  float gain = fsqrt(fdiv(energy2, energy1 + 1.f));
+  const float ratio = fdiv(energy2, energy1 + 1.f);
+  float gain = WAVE_SQRT ? fsqrt_wave(ratio) : fsqrt(ratio);
   if (gain > NS_B_LIM) {
     factor1 = 1.f + 1.3f * (gain - NS_B_LIM);
     if (gain * factor1 > 1.f) factor1 = fdiv(1.f, gain);

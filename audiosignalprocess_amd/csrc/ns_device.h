@@ -139,6 +139,15 @@ __device__ __forceinline__ float fdiv_quot(float n, float d, float r1) {  // r1 
   return __builtin_fmaf(e2, r1, q1);
 }
 __device__ __forceinline__ float fdiv(float n, float d) { return fdiv_quot(n, d, fdiv_rcp(d)); }
+// fdiv(1.f, d) without the quotient's last correction: with n == 1 the quotient's first value IS the refined
+// reciprocal (1 * r1, exact), its first correction is a third Newton step on a value already within an ulp, and the
+// second correction finds nothing left to add.  Equal to fdiv(1.f, d) bit for bit on every float bit pattern (swept on
+// the device, tests/test_ns_fallbacks_gpu.py).
+__device__ __forceinline__ float frcp(float d) {
+  const float r1 = fdiv_rcp(d);
+  const float e1 = __builtin_fmaf(-d, r1, 1.0f);
+  return __builtin_fmaf(e1, r1, r1);
+}
 // Two correctly rounded divisions at a time: the same arithmetic as fdiv with the seven
 // multiply-add steps issued as packed-f32 instructions (one issue slot for two quotients).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -158,6 +167,12 @@ __device__ __forceinline__ f32x2 fdiv2_quot(f32x2 n, f32x2 d, f32x2 r1) {  // r1
   return __builtin_elementwise_fma(e2, r1, q1);
 }
 __device__ __forceinline__ f32x2 fdiv2(f32x2 n, f32x2 d) { return fdiv2_quot(n, d, fdiv2_rcp(d)); }
+__device__ __forceinline__ f32x2 frcp2(f32x2 d) {  // frcp for two, packed
+  const f32x2 one = {1.0f, 1.0f};
+  const f32x2 r1 = fdiv2_rcp(d);
+  const f32x2 e1 = __builtin_elementwise_fma(-d, r1, one);
+  return __builtin_elementwise_fma(e1, r1, r1);
+}
 // Three bins of a lane of the one-stream-per-wave kernel (two owned + bin 128) as one packed pair
 // and a scalar: +, -, * and fma on an F3 compile to v_pk_* for the pair.  Every operation is the IEEE
 // single operation of its scalar spelling (no contraction), so results are bit-identical to per-bin loops.
@@ -344,6 +359,13 @@ __device__ __forceinline__ bool f64_rounds_safely_to_f32(double y) {
   const unsigned lo = (unsigned)__double2loint(y) & 0x1fffffffu;
   return ((lo - 0x0ffffe00u) > 0x400u);
 }
+// Its negation in two instructions, for the wave-level forms below: the left shift drops the three bits the mask
+// removes, and the window [0x0ffffe00, 0x10000200] times 8 is [0x7ffff000, 0x80001000] -- no low word outside it lands
+// inside after the shift, because the 29 kept bits times 8 do not wrap (every 32-bit low word: swept on the device).
+__device__ __forceinline__ bool f64_lo_rounds_unsafely(unsigned lo) { return ((lo << 3) - 0x7ffff000u) <= 0x2000u; }
+__device__ __forceinline__ bool f64_rounds_unsafely_to_f32(double y) {
+  return f64_lo_rounds_unsafely((unsigned)__double2loint(y));
+}
 
 // exp((double)x) for a float x with |x| <= 87 (float result normal), lean fp64:
 // k = rint(64 x / ln 2), r = x - k ln2/64 (|r| <= 0.0055), e^r by a degree-5
@@ -415,8 +437,10 @@ __device__ __forceinline__ float tanh_f32_via_f64(float a, const double* __restr
 // Checked against the libm form for every float bit pattern on the device (tests/test_ns_tanh_wave_gpu.py).
 __device__ __forceinline__ float tanh_f32_via_f64_wave(float a, const double* __restrict__ t64) {
   const float ax = fabsf(a);
-  const bool finite_ok = ax <= 40.0f;  // beyond: |tanh| rounds to 1, left to libm; NaN too
-  const double u = exp_lean_f64(finite_ok ? -2.0f * ax : 0.0f, t64);
+  // beyond 40 |tanh| rounds to 1, left to libm; NaN too.  Such an argument runs through the lean form as it is (the
+  // table index is masked, nothing can fault) and is flagged
+  const unsigned long long far = __builtin_amdgcn_ballot_w64(!(ax <= 40.0f));
+  const double u = exp_lean_f64(-2.0f * ax, t64);
   const double num = 1.0 - u, den = 1.0 + u;
   double rc = (double)__builtin_amdgcn_rcpf((float)den);
   rc = __builtin_fma(__builtin_fma(-den, rc, 1.0), rc, rc);
@@ -433,9 +457,11 @@ __device__ __forceinline__ float tanh_f32_via_f64_wave(float a, const double* __
     const double t_small = __builtin_fma(ad * a2, sr, ad);
     t = small ? t_small : t;
   }
-  const bool ok = finite_ok && f64_rounds_safely_to_f32(t);
+  // the fallback behind ONE wave-level test (one compare per predicate, the lane masks OR-ed as scalars): where some
+  // lane is flagged every lane takes libm's value, which is the lean one wherever that is decided
+  const unsigned long long bad = far | __builtin_amdgcn_ballot_w64(f64_rounds_unsafely_to_f32(t));
   float r = __builtin_copysignf((float)t, a);
-  if (ASP_NS_RARE(!ok)) r = (float)tanh((double)a);
+  if (ASP_NS_RARE(bad != 0)) r = (float)tanh((double)a);
   return r;
 }
 
@@ -543,6 +569,56 @@ __device__ __forceinline__ void exp_f32_via_f64_n(const float (&x)[N], float (&o
     const unsigned in_range = fabsf(x[k]) <= 87.0f ? 1u : 0u;  // false for NaN too
     const double y = exp_lean_f64(x[k], t64);
     bad |= (in_range ^ 1u) | (f64_rounds_safely_to_f32(y) ? 0u : 1u);
+    out[k] = (float)y;
+  }
+  if (ASP_NS_RARE(bad != 0)) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) out[k] = exp_f32_slow(x[k]);
+  }
+}
+
+// The same values with the fallback behind ONE wave-level test (ns_kernels1.hip; the forms above keep their text:
+// ns_kernels.hip and ns_kernels2.hip call them).  Each predicate -- "outside the lean form's range", "the fp64 value
+// sits at a rounding boundary" -- is one compare straight to a lane mask, the masks are OR-ed with scalar
+// instructions and one scalar branch on "any lane" redoes the arguments of ALL lanes of the wave through libm.  That is
+// the contract of the one-argument forms read the other way: where the lean value is decided it equals libm's, so a
+// lane that did not need the fallback receives from it what it had.  The rounding test is the two-instruction form.
+// (tests/test_ns_fallbacks_gpu.py: every float bit pattern against the one-argument forms, alone on a lane among benign
+// arguments and on all lanes.)
+// The wave's lanes whose x is anything but a positive normal float (outside [2^-126, inf): zeros, subnormals, negative
+// values, +inf, NaNs): one class compare, written to a scalar register pair.  (Stated as an instruction because the
+// compiler turns the builtin's result into a lane mask through a select and a second compare.)
+__device__ __forceinline__ unsigned long long lanes_not_positive_normal(float x) {
+  unsigned long long m;
+  asm("v_cmp_class_f32_e64 %0, %1, %2" : "=s"(m) : "v"(x), "s"(0x3ffu & ~0x100u));
+  return m;
+}
+template <int N>
+__device__ __forceinline__ void log_f32_via_tab_n_wave(const float (&x)[N], float (&out)[N],
+                                                       const double2* __restrict__ tab) {
+  unsigned long long bad = 0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    bad |= lanes_not_positive_normal(x[k]);
+    const double y = log_tab_f64(x[k], tab);
+    bad |= __builtin_amdgcn_ballot_w64(f64_rounds_unsafely_to_f32(y));
+    out[k] = (float)y;
+  }
+  if (ASP_NS_RARE(bad != 0)) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) out[k] = log_f32_slow(x[k]);
+  }
+}
+
+template <int N>
+__device__ __forceinline__ void exp_f32_via_f64_n_wave(const float (&x)[N], float (&out)[N],
+                                                       const double* __restrict__ t64) {
+  unsigned long long bad = 0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    bad |= __builtin_amdgcn_ballot_w64(!(fabsf(x[k]) <= 87.0f));  // true for NaN too
+    const double y = exp_lean_f64(x[k], t64);
+    bad |= __builtin_amdgcn_ballot_w64(f64_rounds_unsafely_to_f32(y));
     out[k] = (float)y;
   }
   if (ASP_NS_RARE(bad != 0)) {

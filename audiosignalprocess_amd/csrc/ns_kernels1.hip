@@ -378,6 +378,11 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
   __shared__ __align__(16) double2 logts[128];   // {1/c, log c} of the table-driven log
   // hand-off build: each wave's image of its stream's resident state block (the plain build has no use: no allocation)
   __shared__ __align__(16) float imgs[FLOW ? 4 : 1][FLOW ? kImgDwords : 4];
+  // hand-off build, product kernels: the histogram features of the walk's steady steps that are not yet counted
+  // (hist_flush below): kPendSteps slots of three floats per wave, -1 in a slot that holds nothing
+  constexpr bool DEFER = FLOW && !DIAG;
+  constexpr int kPendSteps = 8, kPendLanes = 3 * kPendSteps;
+  __shared__ __align__(16) float pends[DEFER ? 4 : 1][DEFER ? kPendLanes : 1];
   const int tid = threadIdx.x;
   // ---- prologue: every load of the first phase is issued before the first wait (table pieces
   // first: loads return in order, the LDS staging waits for them only)
@@ -409,6 +414,34 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         atomicAdd(counts + 2 * stream, diag_steps & 0xffffu);
         atomicAdd(counts + 2 * stream + 1, diag_steps >> 16);
       }
+    }
+  };
+
+  // ---- the histogram increments of a walk, once per walk (DEFER).  Past start-up every step adds one count to each
+  // of the three feature histograms (FeatureParameterExtraction(self, 0), ns_core.c:309-334); the counts commute and
+  // are read only where a window closes, which is a generic step.  A step of the steady body therefore only RECORDS
+  // its three feature values, in slot (step of the walk) % kPendSteps of the wave's `pends`; hist_flush() does the bin
+  // arithmetic and the no-return atomic adds for every recorded step at once, slot i's feature f on lane 3 i + f,
+  // through the operations of the per-step form, and empties the slots.  It runs at the walk's end in front of the
+  // write-back and the drain (nothing is pending when the walk is published), in front of everything a generic step
+  // does with the histograms, and in front of every record past the walk's first kPendSteps steps (a longer walk reuses
+  // its slots).  A step that adds nothing now records nothing: the zero-energy exit, and the generic body, which keeps
+  // the per-step form.  (Owner and validity of the slots: DESIGN.md section 4.)
+  lds_f32* const pend = (lds_f32*)pends[DEFER ? wv : 0];
+  auto hist_flush = [&]() __attribute__((always_inline)) {
+    if constexpr (DEFER) {
+      const int lane_c = ns_cold(lane);
+      lds_sync1();
+      if (lane_c < kPendLanes) {
+        const float fv = pend[lane_c];
+        pend[lane_c] = -1.f;
+        const int f = lane_c % 3;  // 0: LRT, 1: spectral flatness, 2: spectral difference
+        const float bw = f == 1 ? 0.05f : 0.1f, rbw = f == 1 ? 1.0f / 0.05f : 1.0f / 0.1f;
+        const float lim = f == 1 ? kHist * 0.05f : kHist * 0.1f;
+        if ((fv < lim) && (fv >= 0.0f))
+          atomicAdd(&hist[f * kHistStride + (int)div_by_uniform(fv, bw, rbw)], 1);  // agent scope (sc1)
+      }
+      lds_sync1();
     }
   };
 
@@ -494,6 +527,9 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
   if constexpr (FLOW) {
     if (wave_live) sa.image_fill(lane, img_v);
   }
+  if constexpr (DEFER) {
+    if (lane < kPendLanes) pends[wv][lane] = -1.f;
+  }
   __syncthreads();
   if (!wave_live) return;
   if constexpr (FLOW) {
@@ -540,7 +576,8 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       NS_BUDGET_ASIDE()                                                                        \
       const int lane_w_ = ns_cold(lane);                                                       \
       srow.store_owned(lane_w_, sv);                                                           \
-      lds_sync1();                                                                             \
+      hist_flush(); /* (orders the image's LDS writes in front of the write-back too) */      \
+      if constexpr (!DEFER) lds_sync1();                                                       \
       sa.image_write_back(lane_w_);                                                            \
       handoff_drain();                                                                         \
     }                                                                                          \
@@ -765,11 +802,11 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         load_snr_tails();
         snr_tail(quant[2]);
         const float xs[NS3] = {magn[0], magn[1], lane == 1 ? 1.f + 2.f * snrLocPrior[2] : magn[2]};
-        log_f32_via_tab_n<NS3>(xs, lmagn, logts);
+        log_f32_via_tab_n_wave<NS3>(xs, lmagn, logts);
         lt1_tail = lane_bcast(lmagn[2], 1);
         lmagn[2] = lane_bcast(lmagn[2], 0);
       } else {
-        log_f32_via_tab_n<NS3>(magn, lmagn, logts);
+        log_f32_via_tab_n_wave<NS3>(magn, lmagn, logts);
       }
       LOADT(avgPause, V_AVGPAUSE)
 
@@ -827,7 +864,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
           counter[s] = 0;
           if (updates >= NS_END_STARTUP_LONG) {
             LQ[s][2] = lane_bcast(lqT, kLqLane + s);  // the publish wants the tail wave-uniform
-            exp_f32_via_f64_n<NS3>(LQ[s], quant, exp2s);
+            exp_f32_via_f64_n_wave<NS3>(LQ[s], quant, exp2s);
             quant_new = true;
           }
         }
@@ -835,7 +872,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       }
       if (updates < NS_END_STARTUP_LONG) {
         LQ[2][2] = lane_bcast(lqT, kLqLane + 2);
-        exp_f32_via_f64_n<NS3>(LQ[2], quant, exp2s);
+        exp_f32_via_f64_n_wave<NS3>(LQ[2], quant, exp2s);
         quant_new = true;
       }
 #pragma unroll
@@ -998,11 +1035,13 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         if constexpr (STEADY) {
           const float t1p[2] = {t1[0], t1[1]};
           float lt1p[2];
+          // (the per-lane form: this is the step's widest point, and the wave-level form of these two chains costs the
+          // hand-off product kernels three spilled vector registers, profiles/README.md)
           log_f32_via_tab_n<2>(t1p, lt1p, logts);
           lt1[0] = lt1p[0]; lt1[1] = lt1p[1];
           lt1[2] = lt1_tail;
         } else {
-          log_f32_via_tab_n<NS3>(t1, lt1, logts);
+          log_f32_via_tab_n_wave<NS3>(t1, lt1, logts);
         }
         float tn[NS3], td3[NS3], t2v[NS3];
 #pragma unroll
@@ -1041,7 +1080,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
 #pragma unroll
         for (int k = 0; k < NS3; ++k) nl[k] = -logLrt[k];
         nl[2] = lane == 0 ? flat.arg : nl[2];
-        exp_f32_via_f64_n<NS3>(nl, ev, exp2s);
+        exp_f32_via_f64_n_wave<NS3>(nl, ev, exp2s);
         {
           const f32x2 qq = fdiv2(f32x2{lane_bcast(ev[2], 0), diffa.n1}, f32x2{flat.den, diffa.d2});
           fd0 = ns_flatness_update_q(fd0, qq.x);  // ns_core.c:551-555
@@ -1056,7 +1095,20 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       int mup0 = updateParsFlag, mup3 = ss.mup3;
       const int mup1 = SC_I(S_MUP1);
       bool window_closed = false;
-      if (updateParsFlag >= 1) {
+      if constexpr (DEFER && !STEADY) hist_flush();  // a generic step counts what is pending, then does what it did
+      if constexpr (STEADY && DEFER) {
+        // the steady body adds in every step (updateParsFlag >= 1, mup3 > 2) and closes no window: the three features
+        // as they stand here go into the step's slot, from lane 0; hist_flush() counts them
+        const unsigned rel = flow_j - blockIdx.y * fa.walk;  // the step of the walk
+        // (past the walk's first kPendSteps steps a slot may be taken -- which ones depends on the zero-energy and
+        // generic steps behind -- so every record counts what is pending first; the product's walks are 4 and 8 steps)
+        if (rel >= (unsigned)kPendSteps) hist_flush();
+        mup3--;
+        if (lane == 0) {
+          lds_f32* const slot = pend + 3 * (rel & (kPendSteps - 1));
+          slot[0] = fd3; slot[1] = fd0; slot[2] = fd4;
+        }
+      } else if (updateParsFlag >= 1) {
         mup3--;
         if (mup3 > 0) {
           // FeatureParameterExtraction(self, 0), ns_core.c:309-334: lanes 0..2 take one histogram each
@@ -1116,14 +1168,16 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         const float gainPrior = fdiv(1.f - priorSpeechProb, priorSpeechProb + 0.0001f);
         {
           float pd[NS3];
-          const float ones[NS3] = {1.f, 1.f, 1.f};
 #pragma unroll
           for (int k = 0; k < NS3; ++k) {
             float invLrt = ev[k];
             invLrt = (float)gainPrior * invLrt;
             pd[k] = 1.f + invLrt;
           }
-          fdiv3(ones, pd, probSpeech);
+          // 1 / pd: the numerator is 1, the reciprocal chain is the quotient's (frcp == fdiv(1.f, .) on every float)
+          const f32x2 ps2 = frcp2(f32x2{pd[0], pd[1]});
+          probSpeech[0] = ps2.x; probSpeech[1] = ps2.y;
+          probSpeech[2] = frcp(pd[2]);
         }
       }
 
@@ -1442,9 +1496,76 @@ __global__ void debug_guards_wave_kernel(unsigned start, unsigned count, unsigne
   }
 }
 
+// Test seam: the steady step's wave-level libm fallbacks and its reciprocal chain, on every 32-bit pattern in [start,
+// start + count), 64 consecutive patterns to a wave.  `what`:
+//   0  the pattern as the low word of an fp64 value: the two-instruction rounding test against the negation of
+//      f64_rounds_safely_to_f32's
+//   1  frcp and both halves of frcp2 against fdiv(1.f, x), bit for bit (NaN payloads included)
+//   2 / 3  log_f32_via_tab_n_wave against log_f32_via_tab: the pattern alone on one lane of the wave with a benign
+//      argument (1.5f) on the 63 others, for each lane in turn -- the others' results are checked too, so a fallback
+//      that one lane provokes must leave them what they had -- / 64 consecutive patterns on the wave's lanes
+//   4 / 5  exp_f32_via_f64_n_wave against exp_f32_via_f64 in the same two arrangements (benign argument: 0.5f)
+// Both sides of every wave-level branch are met: a wave of positive normal (log) or in-range (exp) patterns is flagged
+// in about 2 of 10 000 cases, a wave of negative or NaN patterns always.
+__global__ void debug_fallbacks_wave_kernel(int what, unsigned start, unsigned count, unsigned* n_bad,
+                                            unsigned* bad_bits, const NsTables* __restrict__ T) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = i < count;  // (no early return: the one-lane arrangements loop over the wave's lanes)
+  const unsigned bits = start + (live ? i : 0u);
+  const float x = __uint_as_float(bits);
+  const double2* lt = reinterpret_cast<const double2*>(T->logtab);
+  auto eq = [](float a, float b) { return (__float_as_uint(a) == __float_as_uint(b)) || (a != a && b != b); };
+  bool same = true;
+  if (what == 0) {
+    const unsigned lo = bits & 0x1fffffffu;
+    same = f64_lo_rounds_unsafely(bits) == !((lo - 0x0ffffe00u) > 0x400u);
+  } else if (what == 1) {
+    const float want = fdiv(1.f, x);
+    const f32x2 a = frcp2(f32x2{x, 1.5f}), b = frcp2(f32x2{3.f, x});
+    same = __float_as_uint(frcp(x)) == __float_as_uint(want) && __float_as_uint(a.x) == __float_as_uint(want) &&
+           __float_as_uint(b.y) == __float_as_uint(want) && __float_as_uint(a.y) == __float_as_uint(fdiv(1.f, 1.5f)) &&
+           __float_as_uint(b.x) == __float_as_uint(fdiv(1.f, 3.f));
+  } else if (what == 2 || what == 4) {
+    const bool is_log = what == 2;
+    const float benign = is_log ? 1.5f : 0.5f;
+    const float want = is_log ? log_f32_via_tab(x, lt) : exp_f32_via_f64(x, T->exp2_64);
+    const float want_benign = is_log ? log_f32_via_tab(benign, lt) : exp_f32_via_f64(benign, T->exp2_64);
+    const int lane = threadIdx.x & 63;
+    for (int j = 0; j < 64; ++j) {
+      const float in[1] = {lane == j ? x : benign};
+      float o[1];
+      if (is_log) log_f32_via_tab_n_wave<1>(in, o, lt);
+      else exp_f32_via_f64_n_wave<1>(in, o, T->exp2_64);
+      same = same && eq(o[0], lane == j ? want : want_benign);
+    }
+  } else if (what == 3) {
+    const float in[1] = {x};
+    float o[1];
+    log_f32_via_tab_n_wave<1>(in, o, lt);
+    same = eq(o[0], log_f32_via_tab(x, lt));
+  } else {
+    const float in[1] = {x};
+    float o[1];
+    exp_f32_via_f64_n_wave<1>(in, o, T->exp2_64);
+    same = eq(o[0], exp_f32_via_f64(x, T->exp2_64));
+  }
+  if (live && !same) {
+    const unsigned k = atomicAdd(n_bad, 1u);
+    if (k < 64) bad_bits[k] = bits;
+  }
+}
+
 }  // namespace
 
 namespace aspns {
+
+hipError_t launch_debug_fallbacks_wave(int what, unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits,
+                                       const NsTables* T, hipStream_t s) {
+  if (what < 0 || what > 5) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(debug_fallbacks_wave_kernel, dim3((count + 255u) / 256u), dim3(256), 0, s, what, start, count,
+                     n_bad, bad_bits, T);
+  return hipGetLastError();
+}
 
 hipError_t launch_debug_guards_wave(unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits, hipStream_t s) {
   hipLaunchKernelGGL(debug_guards_wave_kernel, dim3((count + 255u) / 256u), dim3(256), 0, s, start, count, n_bad, bad_bits);

@@ -318,7 +318,8 @@ __device__ __forceinline__ float ns_prior_update(float priorSpeechProb, PriorMod
 }
 
 // Energy-based gain compensation (ns_core.c:1321-1342): the output's scale factor from the frame's energy in front of
-// the filter (energy1) and behind it (energy2).  WAVE_SQRT: the square root in its wave-level form (fsqrt_wave).
+// the filter (energy1) and behind it (energy2).  WAVE_SQRT: the square root in its wave-level form (fsqrt_wave) and
+// 1 / gain through the reciprocal chain (frcp) -- the forms of ns_kernels1.hip; the other kernels' listings stay.
 template <bool WAVE_SQRT = false>
 __device__ __forceinline__ float ns_gain_factor(float energy2, float energy1, float denoiseBound,
                                                 float priorSpeechProb) {
@@ -327,7 +328,7 @@ __device__ __forceinline__ float ns_gain_factor(float energy2, float energy1, fl
   float gain = WAVE_SQRT ? fsqrt_wave(ratio) : fsqrt(ratio);
   if (gain > NS_B_LIM) {
     factor1 = 1.f + 1.3f * (gain - NS_B_LIM);
-    if (gain * factor1 > 1.f) factor1 = fdiv(1.f, gain);
+    if (gain * factor1 > 1.f) factor1 = WAVE_SQRT ? frcp(gain) : fdiv(1.f, gain);  // (equal on every float)
   }
   if (gain < NS_B_LIM) {
     if (gain <= denoiseBound) gain = denoiseBound;

@@ -15,7 +15,8 @@ SOURCES = ["ns_kernels.hip", "ns_kernels1.hip", "ns_kernels2.hip", "ns_kernels_h
            "aec_kernels.hip", "aec_delay_kernels.hip", "aec_api.hip", "qmf_kernels.hip", "qmf_api.hip", "sinc_kernels.hip", "sinc_api.hip",
            "vad_kernels.hip", "vad_api.hip", "aecm_kernels.hip", "aecm_api.hip", "nsx_kernels.hip", "nsx_api.hip",
            "splrs_kernels.hip", "splrs_api.hip", "agc_kernels.hip", "agc_api.hip", "ts_kernels.hip", "ts_api.hip",
-           "bf_kernels.hip", "bf_api.hip", "hpf_kernels.hip", "hpf_api.hip", "level_kernels.hip", "level_api.hip"]
+           "bf_kernels.hip", "bf_api.hip", "hpf_kernels.hip", "hpf_api.hip", "level_kernels.hip", "level_api.hip",
+           "ab_kernels.hip", "ab_api.hip"]
 C_SOURCES = ["wav_io.c"]  # host-only C (kept C, as in the reference)
 # -ffp-contract=off: parity with the reference depends on unfused mul/add.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",
@@ -92,12 +93,12 @@ def build_library(force=False, verbose=False):
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)
         objs.append(o)
-    # the CPU builds of the AECM, NSX, resampler, gain-control, transient-suppressor, beamformer and high-pass filter / level
-    # estimator cores, for the tests only (no CPU path in libasp_amd.so)
+    # the CPU builds of the AECM, NSX, resampler, gain-control, transient-suppressor, beamformer, high-pass filter / level
+    # estimator and audio buffer cores, for the tests only (no CPU path in libasp_amd.so)
     for src_name, so_name in (("aecm_restate.cpp", "libaecm_restate.so"), ("nsx_restate.cpp", "libnsx_restate.so"),
                               ("splrs_restate.cpp", "libsplrs_restate.so"), ("agc_restate.cpp", "libagc_restate.so"),
                               ("ts_restate.cpp", "libts_restate.so"), ("bf_restate.cpp", "libbf_restate.so"),
-                              ("hpf_restate.cpp", "libhpf_restate.so")):
+                              ("hpf_restate.cpp", "libhpf_restate.so"), ("ab_restate.cpp", "libab_restate.so")):
         src = os.path.join(CSRC, src_name)
         so = os.path.join(LIBDIR, so_name)
         if force or _stale(so, [src] + hdrs):

@@ -212,7 +212,7 @@ void WebRtcSpl_SynthesisQMF(const int16_t* low_band, const int16_t* high_band, i
 
 struct AspSplitBatch {
   int C = 0, nb = 0, device = 0;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr, own_stream = nullptr;
   int32_t* st = nullptr;       // [3][C][24]: two_bands_states_, band1_states_, band2_states_
   int16_t *buf640 = nullptr, *low320 = nullptr, *high320 = nullptr, *zeros160 = nullptr;
   int16_t *s_in = nullptr, *s_bands = nullptr;   // staging for host-memory callers
@@ -232,7 +232,8 @@ int AspSplitBatch_Create(AspSplitBatch** out, int num_channels, int num_bands, i
   b->nb = num_bands;
   b->device = device;
   const size_t c = (size_t)num_channels;
-  hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+  hipError_t e = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
+  b->stream = b->own_stream;
   if (e == hipSuccess) e = hipMalloc((void**)&b->st, 3 * c * 24 * sizeof(int32_t));
   if (e == hipSuccess) e = hipMalloc((void**)&b->buf640, c * 640 * sizeof(int16_t));
   if (e == hipSuccess) e = hipMalloc((void**)&b->low320, c * 320 * sizeof(int16_t));
@@ -272,7 +273,7 @@ int AspSplitBatch_Free(AspSplitBatch* b) {
   if (b->zeros160) (void)hipFree(b->zeros160);
   if (b->s_in) (void)hipFree(b->s_in);
   if (b->s_bands) (void)hipFree(b->s_bands);
-  if (b->stream) (void)hipStreamDestroy(b->stream);
+  if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
   delete b;
   return 0;
 }
@@ -338,6 +339,57 @@ int AspSplitBatch_Synthesis(AspSplitBatch* b, const int16_t* bands, int16_t* out
     QMF_TRY(hipMemcpyAsync(out, dout, total, hipMemcpyDeviceToHost, b->stream));
     QMF_TRY(hipStreamSynchronize(b->stream));
   }
+  return ASP_OK;
+}
+
+int AspSplitBatch_SetStream(AspSplitBatch* b, void* hip_stream) {
+  AspDeviceScope dev_scope_;
+  if (!b) return qmf_fail(ASP_ERR_PARAM, "null batch handle");
+  QMF_TRY(dev_scope_.select(b->device));
+  QMF_TRY(hipStreamSynchronize(b->stream));
+  b->stream = hip_stream ? (hipStream_t)hip_stream : b->own_stream;
+  int rc = ASP_OK;
+  if (b->up) rc = AspSincBatch_SetStream(b->up, b->stream);
+  if (rc == ASP_OK && b->down) rc = AspSincBatch_SetStream(b->down, b->stream);
+  return rc;
+}
+
+int AspSplitBatch_Synchronize(AspSplitBatch* b) {
+  AspDeviceScope dev_scope_;
+  if (!b) return qmf_fail(ASP_ERR_PARAM, "null batch handle");
+  QMF_TRY(dev_scope_.select(b->device));
+  QMF_TRY(hipStreamSynchronize(b->stream));
+  return ASP_OK;
+}
+
+int AspSplitBatch_ExportState(AspSplitBatch* b, int channel, AspSplitState* out) {
+  AspDeviceScope dev_scope_;
+  if (!b || !out || channel < 0 || channel >= b->C) return qmf_fail(ASP_ERR_PARAM, "AspSplitBatch_ExportState: bad argument");
+  QMF_TRY(dev_scope_.select(b->device));
+  memset(out, 0, sizeof *out);
+  for (int k = 0; k < 3; ++k)
+    QMF_TRY(hipMemcpyAsync(&out->qmf[k], b->st + ((size_t)k * b->C + channel) * 24, sizeof(AspQmfState),
+                           hipMemcpyDeviceToHost, b->stream));
+  QMF_TRY(hipStreamSynchronize(b->stream));
+  if (b->nb == 3) {
+    if (int rc = AspSincBatch_ExportState(b->up, channel, out->up_buffer, &out->up_pos)) return rc;
+    if (int rc = AspSincBatch_ExportState(b->down, channel, out->down_buffer, &out->down_pos)) return rc;
+  }
+  return ASP_OK;
+}
+
+int AspSplitBatch_ImportState(AspSplitBatch* b, int channel, const AspSplitState* in) {
+  AspDeviceScope dev_scope_;
+  if (!b || !in || channel < 0 || channel >= b->C) return qmf_fail(ASP_ERR_PARAM, "AspSplitBatch_ImportState: bad argument");
+  QMF_TRY(dev_scope_.select(b->device));
+  if (b->nb == 3) {  // the resamplers first: they are what can refuse
+    if (int rc = AspSincBatch_ImportState(b->up, channel, in->up_buffer, &in->up_pos)) return rc;
+    if (int rc = AspSincBatch_ImportState(b->down, channel, in->down_buffer, &in->down_pos)) return rc;
+  }
+  for (int k = 0; k < 3; ++k)
+    QMF_TRY(hipMemcpyAsync(b->st + ((size_t)k * b->C + channel) * 24, &in->qmf[k], sizeof(AspQmfState),
+                           hipMemcpyHostToDevice, b->stream));
+  QMF_TRY(hipStreamSynchronize(b->stream));
   return ASP_OK;
 }
 

@@ -14,6 +14,7 @@
 #include "asp_ns.h"
 #include "asp_resample.h"
 #include "sinc_layout.h"
+#include "sinc_plan.h"
 
 using namespace aspsinc;
 
@@ -49,94 +50,6 @@ struct AspSincBatch {
   int r0 = 0, r3 = 0, r4 = 0, block_size = 0;
   bool primed = false, first_pass = true;
 };
-
-namespace {
-
-void update_regions(AspSincBatch* b, bool second_load) {  // sinc_resampler.cc:190-199
-  b->r0 = second_load ? kKernelSize : kKernelSize / 2;
-  b->r3 = b->r0 + b->src - kKernelSize;
-  b->r4 = b->r0 + b->src - kKernelSize / 2;
-  b->block_size = b->r4 - kKernelSize / 2;
-}
-
-// NOTE: C++ translation unit; libm calls take explicit doubles so the arithmetic is the reference's.
-void init_kernel(AspSincBatch* b) {  // sinc_resampler.cc:201-232, 88-101
-  const double kAlpha = 0.16;
-  const double kA0 = 0.5 * (1.0 - kAlpha), kA1 = 0.5, kA2 = 0.5 * kAlpha;
-  double sinc_scale_factor = b->ratio > 1.0 ? 1.0 / b->ratio : 1.0;
-  sinc_scale_factor *= 0.9;
-  b->kernel_host.assign((size_t)kKernelSize * (kKernelOffsetCount + 1), 0.f);
-  for (int offset_idx = 0; offset_idx <= kKernelOffsetCount; ++offset_idx) {
-    const float subsample_offset = static_cast<float>(offset_idx) / kKernelOffsetCount;
-    for (int i = 0; i < kKernelSize; ++i) {
-      const int idx = i + offset_idx * kKernelSize;
-      const float pre_sinc = static_cast<float>(M_PI * (double)(i - kKernelSize / 2 - subsample_offset));
-      const float x = (i - subsample_offset) / kKernelSize;
-      const float window = static_cast<float>(kA0 - kA1 * cos(2.0 * M_PI * (double)x) + kA2 * cos(4.0 * M_PI * (double)x));
-      b->kernel_host[idx] = static_cast<float>(
-          (double)window * ((pre_sinc == 0) ? sinc_scale_factor
-                                            : (sin(sinc_scale_factor * (double)pre_sinc) / (double)pre_sinc)));
-    }
-  }
-}
-
-// SincResampler::Resample(frames, destination) as a plan: appends segments / descriptors.
-// dest_base >= 0: outputs land at dest_base + k of the caller's buffer; < 0: discarded.
-int plan_resample(AspSincBatch* b, int frames, int dest_base, SincPlan* plan) {
-  int remaining = frames, produced = 0;
-  auto open_seg = [&](int load, int shift) -> SincSeg* {
-    if (plan->nseg >= 6) return nullptr;
-    SincSeg* sg = &plan->seg[plan->nseg++];
-    sg->load = load;
-    sg->shift = shift;
-    sg->r0 = b->r0;
-    sg->r3 = b->r3;
-    sg->out_begin = sg->out_end = (int)b->desc_host.size();
-    return sg;
-  };
-  SincSeg* cur = nullptr;
-  if (!b->primed && remaining) {  // read_cb_->Run(request_frames_, r0_)
-    cur = open_seg(b->first_pass ? 1 : 2, 0);
-    if (!cur) return sinc_fail(ASP_ERR_STATE, "resampler plan: too many segments");
-    b->first_pass = false;
-    b->primed = true;
-  }
-  if (!cur) {
-    cur = open_seg(0, 0);
-    if (!cur) return sinc_fail(ASP_ERR_STATE, "resampler plan: too many segments");
-  }
-  while (remaining) {
-    for (int i = (int)ceil((b->block_size - b->vsi) / b->ratio); i > 0; --i) {
-      const int source_idx = (int)b->vsi;
-      const double subsample_remainder = b->vsi - source_idx;
-      const double virtual_offset_idx = subsample_remainder * kKernelOffsetCount;
-      const int offset_idx = (int)virtual_offset_idx;
-      const double factor = virtual_offset_idx - offset_idx;
-      OutDesc d;
-      d.source_idx = source_idx;
-      d.offset_idx = offset_idx;
-      d.f1 = static_cast<float>(1.0 - factor);
-      d.f2 = static_cast<float>(factor);
-      d.dest = dest_base >= 0 ? dest_base + produced : -1;
-      b->desc_host.push_back(d);
-      cur->out_end = (int)b->desc_host.size();
-      ++produced;
-      b->vsi += b->ratio;
-      if (!--remaining) return 0;
-    }
-    b->vsi -= b->block_size;
-    const int r3_before = b->r3;
-    if (b->r0 == kKernelSize / 2) update_regions(b, true);
-    const int load = b->first_pass ? 1 : 2;
-    b->first_pass = false;
-    cur = open_seg(load, 1);
-    if (!cur) return sinc_fail(ASP_ERR_STATE, "resampler plan: too many segments");
-    cur->r3 = r3_before;  // the shift reads the region of the block just consumed
-  }
-  return 0;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -218,11 +131,7 @@ int AspSincBatch_Resample(AspSincBatch* b, const int16_t* in, int16_t* out, int 
   // PushSincResampler::Resample (push_sinc_resampler.cc:47-60): a priming pass on the first call
   SincPlan plan;
   memset(&plan, 0, sizeof plan);
-  b->desc_host.clear();
-  int rc = 0;
-  if (b->first_pass) rc = plan_resample(b, (int)(b->block_size / b->ratio), -1, &plan);  // ChunkSize()
-  if (rc == 0) rc = plan_resample(b, b->dst, 0, &plan);
-  if (rc != 0) return rc;
+  if (!plan_push(b, &plan)) return sinc_fail(ASP_ERR_STATE, "resampler plan: too many segments");
   const int16_t* din = in;
   int16_t* dout = out;
   if (mem == ASP_MEM_HOST) {
@@ -263,6 +172,36 @@ int AspSincBatch_Synchronize(AspSincBatch* b) {
   SINC_TRY(hipStreamSynchronize(b->stream));
   return ASP_OK;
 }
+
+static_assert(sizeof(AspSincPos) == sizeof(SincPos), "AspSincPos is SincPos");
+
+int AspSincBatch_ExportState(AspSincBatch* b, int channel, float* buffer, AspSincPos* pos) {
+  AspDeviceScope dev_scope_;
+  if (!b || channel < 0 || channel >= b->C || !buffer || !pos) return sinc_fail(ASP_ERR_PARAM, "ExportState: bad argument");
+  SINC_TRY(dev_scope_.select(b->device));
+  SINC_TRY(hipMemcpyAsync(buffer, b->state + (size_t)channel * b->buf_len, b->buf_len * sizeof(float), hipMemcpyDeviceToHost,
+                          b->stream));
+  SINC_TRY(hipStreamSynchronize(b->stream));
+  const SincPos p = get_pos(b);
+  memcpy(pos, &p, sizeof p);
+  return ASP_OK;
+}
+
+int AspSincBatch_ImportState(AspSincBatch* b, int channel, const float* buffer, const AspSincPos* pos) {
+  AspDeviceScope dev_scope_;
+  if (!b || channel < 0 || channel >= b->C || !buffer || !pos) return sinc_fail(ASP_ERR_PARAM, "ImportState: bad argument");
+  SincPos p;
+  memcpy(&p, pos, sizeof p);
+  if (!same_pos(p, get_pos(b)))
+    return sinc_fail(ASP_ERR_STATE, "AspSincBatch_ImportState: the position record differs from the batch's");
+  SINC_TRY(dev_scope_.select(b->device));
+  SINC_TRY(hipMemcpyAsync(b->state + (size_t)channel * b->buf_len, buffer, b->buf_len * sizeof(float), hipMemcpyHostToDevice,
+                          b->stream));
+  SINC_TRY(hipStreamSynchronize(b->stream));
+  return ASP_OK;
+}
+
+int AspSincBatch_buffer_length(const AspSincBatch* b) { return b ? b->buf_len : 0; }
 
 int AspSincBatch_kernel_table(const AspSincBatch* b, float* out, int capacity) {
   AspDeviceScope dev_scope_;

@@ -38,6 +38,19 @@ int AspSincBatch_SetStream(AspSincBatch* b, void* hip_stream);
  * tests.  Returns the number of floats written (1056). */
 int AspSincBatch_kernel_table(const AspSincBatch* b, float* out, int capacity);
 
+/* Checkpoint.  A channel's state is its input buffer (AspSincBatch_buffer_length floats: source_frames + 32,
+ * SincResampler::input_buffer_); the position of the call sequence (virtual_source_idx_, the region offsets, the
+ * priming flags) is one record for the whole batch.  Import copies the buffer and is refused with ASP_ERR_STATE
+ * when the record differs from the receiving batch's: advance that batch by the same number of calls first. */
+typedef struct AspSincPos {
+  double virtual_source_idx;
+  int32_t r0, r3, r4, block_size;
+  int32_t primed, first_pass;
+} AspSincPos;
+int AspSincBatch_buffer_length(const AspSincBatch* b);
+int AspSincBatch_ExportState(AspSincBatch* b, int channel, float* buffer, AspSincPos* pos);
+int AspSincBatch_ImportState(AspSincBatch* b, int channel, const float* buffer, const AspSincPos* pos);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "asp_resample.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -65,6 +67,20 @@ int AspSplitBatch_Free(AspSplitBatch* b);
 /* in [num_channels][160 * num_bands] int16 -> bands [num_bands][num_channels][160]. */
 int AspSplitBatch_Analysis(AspSplitBatch* b, const int16_t* in, int16_t* bands, int mem);
 int AspSplitBatch_Synthesis(AspSplitBatch* b, const int16_t* bands, int16_t* out, int mem);
+/* Run the batch on the caller's HIP stream (hipStream_t as void*) instead of its own; NULL: its own. */
+int AspSplitBatch_SetStream(AspSplitBatch* b, void* hip_stream);
+int AspSplitBatch_Synchronize(AspSplitBatch* b);
+
+/* Checkpoint of one channel: two_bands_states_, band1_states_ and band2_states_, and with three bands the input
+ * buffers and position records of the 48 -> 64 and 64 -> 48 kHz resamplers (zero with two bands).  Import is
+ * refused with ASP_ERR_STATE when a position record differs from the receiving batch's (asp_resample.h). */
+typedef struct AspSplitState {
+  AspQmfState qmf[3];
+  AspSincPos up_pos, down_pos;
+  float up_buffer[480 + 32], down_buffer[640 + 32];
+} AspSplitState;
+int AspSplitBatch_ExportState(AspSplitBatch* b, int channel, AspSplitState* out);
+int AspSplitBatch_ImportState(AspSplitBatch* b, int channel, const AspSplitState* in);
 
 #ifdef __cplusplus
 }

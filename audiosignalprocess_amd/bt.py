@@ -98,6 +98,11 @@ class BtBatch:
                "AspBtBatch_DenoiseBlocks")
         return y
 
+    def denoise_blocks_device(self, in_ptr, out_ptr, nblocks):
+        """denoise_blocks() on device memory ([nblocks][S][macro] float32 each; see include/asp_bt.h on overlap)."""
+        _check(self.lib.AspBtBatch_DenoiseBlocks(self.h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), nblocks, MEM_DEVICE),
+               "AspBtBatch_DenoiseBlocks")
+
     def reset_stream(self, stream):
         """blockThreshold_reset of one stream-channel of the running batch."""
         _check(self.lib.AspBtBatch_ResetStream(self.h, stream), "AspBtBatch_ResetStream")

@@ -243,10 +243,18 @@ struct AspBtBatch {
 };
 
 namespace {
-bool bt_flow_applies(const AspBtBatch* b, int steps, const float* in, float* out) {
+// `ring`: the macroblock slots of in / out the call may touch ([ring][num_streams][macro] each)
+bool bt_flow_applies(const AspBtBatch* b, int steps, const float* in, float* out, int ring) {
   const bool on = b->flow < 0 ? handoff_env_default("ASP_BT_FLOW") : b->flow != 0;
+  // Overlapping in / out take one launch per macroblock.  The hand-off build reads a step's input tail from the
+  // previous macroblock's INPUT slot, which the previous step overwrites once out shares memory with in; the plain
+  // kernels read all of a macroblock's input (and carry its tail into the state) ahead of their first output store,
+  // and launches run in order, so there the call is what `steps` Denoise calls on the same pointers are.
+  const size_t span = (size_t)b->S * b->macro * (size_t)ring * sizeof(float);
+  const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
+  const bool overlap = i0 < o0 + span && o0 < i0 + span;
   // the tuned kernels' windows, 8-byte aligned frames (their 8-byte accesses), whole groups of four at 256 samples
-  return on && steps >= 2 && !b->any && (b->win == 1024 || (b->win == 256 && b->S % 4 == 0)) &&
+  return on && !overlap && steps >= 2 && !b->any && (b->win == 1024 || (b->win == 256 && b->S % 4 == 0)) &&
          ((uintptr_t)in & 7) == 0 && ((uintptr_t)out & 7) == 0;
 }
 int bt_flow_steps(AspBtBatch* b, const float* in, float* out, int ring, int steps) {
@@ -446,7 +454,7 @@ int AspBtBatch_DenoiseBlocks(AspBtBatch* b, const float* in, float* out, int nbl
     dout = tmp_out;
   }
   int rc = ASP_OK;
-  if (bt_flow_applies(b, nblocks, din, dout)) {
+  if (bt_flow_applies(b, nblocks, din, dout, nblocks)) {
     rc = bt_flow_steps(b, din, dout, nblocks, nblocks);
   } else {
     for (int k = 0; k < nblocks && rc == ASP_OK; ++k)
@@ -472,7 +480,7 @@ int AspBtBatch_TimedSteps(AspBtBatch* b, const float* in, float* out, int blocks
     return bt_fail(ASP_ERR_PARAM, "TimedSteps: bad argument");
   BT_TRY(dev_scope_.select(b->device));
   const size_t per = (size_t)b->S * b->macro;
-  if (bt_flow_applies(b, steps, in, out)) {
+  if (bt_flow_applies(b, steps, in, out, blocks_in_ring)) {
     BT_TRY(hipEventRecord(b->ev0, b->stream));
     const int rcf = bt_flow_steps(b, in, out, blocks_in_ring, steps);
     if (rcf != ASP_OK) return rcf;

@@ -650,8 +650,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, 
   __syncthreads();
   BT8_STAMP(4)
   // carry the last HALF input samples (wave 0 has read the old tail before the barrier); hand-off build: only the
-  // launch's last step (the steps in between read them from their predecessor's input)
-  if (!flow_last) {
+  // launch's last step (the steps in between read them from their predecessor's input), and only at the end of the
+  // kernel, behind the hand-off: the launch's FIRST step reads the state's copy, and nothing but the chain of
+  // sequence waits orders this workgroup behind that one
+  if constexpr (FLOW) {
   } else if constexpr (Q4) {
     const size_t sq4 = (size_t)4 * blockIdx.x + (tid >> 7);
     state[sq4 * kStateFloats + kOffInTail + (tid & 127)] = in[sq4 * in_stride + 7 * HALFV + (tid & 127)];
@@ -908,6 +910,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, 
       if (lane == 0) handoff_publish(fa.hand.seq + blockIdx.x, flow_want);
     }
   }
+  }
+  if constexpr (FLOW) {
+    // the launch's last step carries the input tail into the state.  Wave 0's sequence wait has succeeded two
+    // barriers ago: every earlier step of this stream-channel has published, the launch's first one included, and
+    // that one read the state's copy in its phase A
+    if (!flow_last) {
+    } else if constexpr (Q4) {
+      const size_t sq4 = (size_t)4 * blockIdx.x + (tid >> 7);
+      state[sq4 * kStateFloats + kOffInTail + (tid & 127)] = in[sq4 * in_stride + 7 * HALFV + (tid & 127)];
+    } else {
+      st[kOffInTail + tid] = x[7 * HALF + tid];
+    }
   }
   BT8_STAMP(10)
   BT8_WSTAMP(3)

@@ -72,7 +72,14 @@ int AspBtBatch_ResetStream(AspBtBatch* b, int stream);
  * [nblocks][num_streams][macro_size] float32.  With 256- and 1024-sample windows the macroblocks of up to 64 steps
  * go into ONE launch (the hand-off build: a stream-channel's input tail is read from the previous macroblock's
  * input, its overlap-add tail is handed on through memory behind a per-stream counter); results are those of
- * nblocks AspBtBatch_Denoise calls, bit for bit.  AspBtBatch_SetFlow: -1 default (on; ASP_BT_FLOW=0 in the
+ * nblocks AspBtBatch_Denoise calls, bit for bit.  Overlapping buffers: the call is always what nblocks Denoise calls on
+ * in + k * num_streams * macro_size, out + k * num_streams * macro_size (k = 0 .. nblocks - 1, in that order) are.  A
+ * Denoise call reads a stream-channel's input ahead of that stream-channel's first output store, so out == in works
+ * in place, and so does out a whole number of macroblock slots (num_streams * macro_size) below in; with out above in
+ * a later macroblock reads what an earlier one wrote, and any other offset is undefined.  When [in, in + nblocks *
+ * num_streams * macro_size) and the same range of out share memory the hand-off build is not used (it reads a
+ * macroblock's input tail from the previous macroblock's input); the same holds for AspBtBatch_TimedSteps over its
+ * blocks_in_ring slots.  AspBtBatch_SetFlow: -1 default (on; ASP_BT_FLOW=0 in the
  * environment turns the default off), 0 off (one launch per macroblock), 1 on. */
 int AspBtBatch_DenoiseBlocks(AspBtBatch* b, const float* in, float* out, int nblocks, int mem);
 int AspBtBatch_SetFlow(AspBtBatch* b, int mode);

@@ -5,10 +5,13 @@
  * 4, 2, 3, 5 and the generic butterfly -- so any even window length).
  * TEST INFRASTRUCTURE ONLY -- see bt_oracle.h.
  *
- * PARITY UNPINNED for the FFT internals: common/kiss_fft/_kiss_fft_guts.h is
- * missing from the reference snapshot, so kiss_fft -- and with it the whole
- * BlockThresholding program -- cannot be compiled here without writing a
- * stand-in header, and the reference ships no expected outputs for it
+ * Parity: everything above the FFT is pinned -- audioDenoiseBlockTreshold.c
+ * compiles in place once its three kiss_fft symbols are supplied, and
+ * ref_probe_bt.c builds it that way with this file's FFT underneath; this
+ * restatement equals that build bit for bit (tests/test_bt_oracle.py).
+ * NOT pinned: the FFT internals.  common/kiss_fft/_kiss_fft_guts.h is missing
+ * from the reference snapshot, so kiss_fft cannot be compiled without writing
+ * a stand-in header, and the reference ships no expected outputs for it
  * (unittest_fft.cpp / unittest_real_fft.cpp only print).  The complex
  * multiply / add macros are restated from their uses in kiss_fft.c:21-90 and
  * kiss_fftr.c:92-157 (upstream kissfft 1.3.0 semantics: C_MUL is the plain
@@ -405,7 +408,7 @@ static float column_power(const BtOracle* h, cpx* base, int col) {
 
 /* blockThreshold_adaptive_block (.c:354-419) + blockTreshold_compute_thre (.c:421-454)
  * for macro-column m (bins 1+16m .. 16+16m). */
-static void macro_column(BtOracle* h, int m, int* seg_out) {
+static void macro_column(BtOracle* h, int m, int* seg_out, float* sure_out) {
   cpx blk[NT][NF];
   float nrm[NT][NF]; /* real parts of stft_coef_block_norm */
   float SURE[3][5];
@@ -448,6 +451,7 @@ static void macro_column(BtOracle* h, int m, int* seg_out) {
     seg_out[2 * m] = seg_time;
     seg_out[2 * m + 1] = seg_freq;
   }
+  if (sure_out) memcpy(sure_out + 15 * m, SURE, sizeof SURE);
   /* compute_thre */
   const int TT = NT >> seg_time, FF = NF >> seg_freq;
   const float lambda = m_lambda[seg_time][seg_freq];
@@ -469,7 +473,7 @@ static void macro_column(BtOracle* h, int m, int* seg_out) {
     }
 }
 
-static void bt_core(BtOracle* h, int* seg_out) { /* blockThreshold_core, .c:488-539 */
+static void bt_core(BtOracle* h, int* seg_out, float* sure_out) { /* blockThreshold_core, .c:488-539 */
   const float L_pi = 8.0, Lambda_pi = 2.5;
   const int ncol = (h->win - 1) / 2 / NF;
   float a;
@@ -479,7 +483,7 @@ static void bt_core(BtOracle* h, int* seg_out) { /* blockThreshold_core, .c:488-
     row(h->thre, h, t)[0].r = row(h->coef, h, t)[0].r * a;
     row(h->thre, h, t)[0].i = row(h->coef, h, t)[0].i * a;
   }
-  for (int m = 0; m < ncol; m++) macro_column(h, m, seg_out);
+  for (int m = 0; m < ncol; m++) macro_column(h, m, seg_out, sure_out);
   for (int i = 1 + ncol * NF; i < h->win / 2 + 1; i++) { /* .c:518-532 */
     a = Lambda_pi * L_pi * POW2(h->sigma_h) * (h->win);
     a = 1 - a / column_power(h, h->coef, i);
@@ -516,7 +520,7 @@ int bt_oracle_denoise_float(BtOracle* h, const float* in, int in_len) { /* .c:54
   kiss_fftr_fwd(&h->fft, h->inbuf_win, row(h->coef, h, h->have));
   h->have++;
   if (h->have != NT) return MARS_NEED_MORE_SAMPLES;
-  bt_core(h, NULL);
+  bt_core(h, NULL, NULL);
   overlap_add(h, NT);
   h->have = 0;
   return MARS_CAN_OUTPUT;
@@ -547,6 +551,25 @@ int16_t bt_oracle_float_to_s16(float v) {
   return v <= -1 ? (-32768) : (int16_t)(-v * (-32768) - 0.5);
 }
 
+void bt_oracle_s16_to_float_n(const int16_t* v, float* out, int n) {
+  for (int i = 0; i < n; ++i) out[i] = bt_oracle_s16_to_float(v[i]);
+}
+void bt_oracle_float_to_s16_n(const float* v, int16_t* out, int n) {
+  for (int i = 0; i < n; ++i) out[i] = bt_oracle_float_to_s16(v[i]);
+}
+
+/* The core alone, on caller-supplied spectra (the seam the reference build is probed at as well,
+ * ref_probe_bt.c): coef [8][win/2 + 1] interleaved {r, i} is replaced by stft_coef after the Wiener
+ * step, thre receives stft_thre, seg (seg_time, seg_freq) and sure the 3 x 5 SURE matrix of every
+ * macro-column.  The handle's framing state is not touched. */
+void bt_oracle_core(BtOracle* h, float* coef, float* thre, int* seg, float* sure) {
+  const size_t bytes = sizeof(cpx) * (size_t)NT * (h->win / 2 + 1);
+  memcpy(h->coef, coef, bytes);
+  bt_core(h, seg, sure);
+  memcpy(coef, h->coef, bytes);
+  memcpy(thre, h->thre, bytes);
+}
+
 /* One whole macroblock (8 hops) of one stream; seg_out (optional) receives the
  * chosen (seg_time, seg_freq) of every macro-column. */
 void bt_oracle_macroblock(BtOracle* h, const float* in, float* out, int* seg_out) {
@@ -556,7 +579,7 @@ void bt_oracle_macroblock(BtOracle* h, const float* in, float* out, int* seg_out
     for (int i = 0; i < h->win; i++) h->inbuf_win[i] = h->inbuf[i] * h->hann[i];
     kiss_fftr_fwd(&h->fft, h->inbuf_win, row(h->coef, h, t));
   }
-  bt_core(h, seg_out);
+  bt_core(h, seg_out, NULL);
   overlap_add(h, NT);
   memcpy(out, h->outbuf, sizeof(float) * (size_t)h->macro);
   h->have = 0;

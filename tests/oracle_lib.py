@@ -285,6 +285,8 @@ def _dl_object(addr):
 from audiosignalprocess_amd._abi import AspBtState  # noqa: E402
 
 
+_i16p = np.ctypeslib.ndpointer(dtype=np.int16, flags="C_CONTIGUOUS")
+_i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _bt_ready = False
 _bt_lock = __import__("threading").Lock()
 
@@ -314,6 +316,9 @@ def _bt_lib():
             lib.bt_oracle_s16_to_float.argtypes = [C.c_int16]
             lib.bt_oracle_float_to_s16.restype = C.c_int16
             lib.bt_oracle_float_to_s16.argtypes = [C.c_float]
+            lib.bt_oracle_s16_to_float_n.argtypes = [_i16p, _f32p, C.c_int]
+            lib.bt_oracle_float_to_s16_n.argtypes = [_f32p, _i16p, C.c_int]
+            lib.bt_oracle_core.argtypes = [C.c_void_p, _f32p, _f32p, _i32p, _f32p]
             _bt_ready = True
     return lib
 
@@ -363,6 +368,9 @@ class OracleBt:
         got = self.lib.bt_oracle_flush_float(self.h, out, n)
         return got, out[:max(got, 0)]
 
+    def reset(self):
+        self.lib.bt_oracle_reset(self.h)
+
     def export_state(self):
         s = AspBtState()
         self.lib.bt_oracle_export(self.h, C.byref(s))
@@ -385,6 +393,168 @@ class OracleBt:
 
     def hann(self):
         return np.ctypeslib.as_array(self.lib.bt_oracle_hann(self.h), shape=(self.win,)).copy()
+
+    def s16_to_float(self, v):
+        v = np.ascontiguousarray(v, np.int16).reshape(-1)
+        out = np.empty(v.size, np.float32)
+        self.lib.bt_oracle_s16_to_float_n(v, out, v.size)
+        return out
+
+    def float_to_s16(self, v):
+        v = np.ascontiguousarray(v, np.float32).reshape(-1)
+        out = np.empty(v.size, np.int16)
+        self.lib.bt_oracle_float_to_s16_n(v, out, v.size)
+        return out
+
+    def core(self, coef):
+        """blockThreshold_core on spectra coef [8][win/2 + 1] complex64 -> (coef after the Wiener step, thresholded
+        spectra, seg [ncol][2], SURE [ncol][3][5])."""
+        return _bt_core_call(self.lib.bt_oracle_core, self.h, self.win, coef)
+
+
+def _bt_core_call(fn, h, win, coef):
+    nb, ncol = win // 2 + 1, (win - 1) // 2 // 16
+    c = np.ascontiguousarray(coef, np.complex64).copy()
+    assert c.shape == (8, nb)
+    thre = np.empty_like(c)
+    seg = np.zeros((max(ncol, 1), 2), np.int32)
+    sure = np.zeros((max(ncol, 1), 3, 5), np.float32)
+    fn(h, c.view(np.float32).reshape(-1), thre.view(np.float32).reshape(-1), seg.reshape(-1), sure.reshape(-1))
+    return c, thre, seg[:ncol], sure[:ncol]
+
+
+# BlockThresholding reference: audioDenoiseBlockTreshold.c compiled in place, its three kiss_fft symbols forwarded
+# to the oracle's FFT (oracle/ref_probe_bt.c; oracle/_ref/libbt_ref.so)
+BT_REF_SO = os.path.join(ORACLE_DIR, "_ref", "libbt_ref.so")
+_bt_ref = None
+
+
+def have_bt_ref():
+    return os.path.exists(BT_REF_SO)
+
+
+class RefBt:
+    """One handle of the compiled reference denoiser, through its own blockThreshold_* protocol."""
+
+    def __init__(self, time_win=None, fs=16000, win_size=None):
+        global _bt_ref
+        if _bt_ref is None:
+            lib = C.CDLL(BT_REF_SO)
+            vp, i32 = C.c_void_p, C.c_int32
+            lib.blockThreshold_init.restype = vp
+            lib.blockThreshold_init.argtypes = [i32, i32, C.POINTER(i32)]
+            lib.blockThreshold_reset.argtypes = [vp]
+            lib.blockThreshold_denoise_float.argtypes = [vp, _f32p, i32]
+            lib.blockThreshold_output_float.argtypes = [vp, _f32p, i32]
+            lib.blockThreshold_flush_float.argtypes = [vp, _f32p, i32]  # the definition's int16_t* holds floats (.c:648-671)
+            lib.blockThreshold_denoise_int16.argtypes = [vp, _i16p, i32]
+            lib.blockThreshold_output_int16.argtypes = [vp, _i16p, i32]
+            lib.blockThreshold_flush_int16.argtypes = [vp, _i16p, i32]
+            lib.blockThreshold_max_output.argtypes = [vp]
+            lib.blockThreshold_samples_per_time.argtypes = [vp]
+            lib.ref_bt_free.argtypes = [vp]
+            for n in ("ref_bt_win", "ref_bt_have"):
+                getattr(lib, n).argtypes = [vp]
+            for n in ("ref_bt_hann", "ref_bt_inbuf", "ref_bt_outbuf"):
+                getattr(lib, n).argtypes = [vp]
+                getattr(lib, n).restype = C.POINTER(C.c_float)
+            lib.ref_bt_s16_to_float.argtypes = [_i16p, _f32p, C.c_int]
+            lib.ref_bt_float_to_s16.argtypes = [_f32p, _i16p, C.c_int]
+            lib.ref_bt_core.argtypes = [vp, _f32p, _f32p, _i32p, _f32p]
+            lib.ref_bt_coef.argtypes = [vp, C.c_int, _f32p]
+            _bt_ref = lib
+        self.lib = _bt_ref
+        if win_size is not None:  # the (time_win, fs) pair that gives it: fs / 1000 * time_win (.c:91)
+            assert time_win is None
+            time_win, fs = win_size, 1000
+        err = C.c_int32(-1)
+        self.h = self.lib.blockThreshold_init(time_win, fs, C.byref(err))
+        self.err = err.value
+        if self.h is None or self.err != 0:
+            return
+        self.win = self.lib.ref_bt_win(self.h)
+        self.half, self.macro = self.win // 2, 4 * self.win
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.err == 0:
+            self.lib.ref_bt_free(self.h)
+            self.h = None
+
+    def reset(self):
+        return self.lib.blockThreshold_reset(self.h)
+
+    def max_output(self):
+        return self.lib.blockThreshold_max_output(self.h)
+
+    def samples_per_time(self):
+        return self.lib.blockThreshold_samples_per_time(self.h)
+
+    def denoise_float(self, hop):
+        return self.lib.blockThreshold_denoise_float(self.h, np.ascontiguousarray(hop, np.float32), len(hop))
+
+    def denoise_int16(self, hop):
+        return self.lib.blockThreshold_denoise_int16(self.h, np.ascontiguousarray(hop, np.int16), len(hop))
+
+    def _out(self, fn, dtype, n, fill):
+        out = np.full(max(self.macro if n is None else n, 1), fill, dtype)
+        return fn(self.h, out, self.macro if n is None else n), out
+
+    def output_float(self, n=None):
+        return self._out(self.lib.blockThreshold_output_float, np.float32, n, 0)
+
+    def output_int16(self, n=None):
+        return self._out(self.lib.blockThreshold_output_int16, np.int16, n, 0)
+
+    def flush_float(self, n):
+        got, out = self._out(self.lib.blockThreshold_flush_float, np.float32, n, 0)
+        return got, out[:max(got, 0)]
+
+    def flush_int16(self, n):
+        got, out = self._out(self.lib.blockThreshold_flush_int16, np.int16, n, 0)
+        return got, out[:max(got, 0)]
+
+    def run(self, x):
+        """x [k * macro] float32 hop by hop through denoise_float / output_float -> denoised, same length."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = []
+        for hop in x.reshape(-1, self.half):
+            if self.denoise_float(hop) == 0x20:
+                out.append(self.output_float()[1])
+        return np.concatenate(out)
+
+    def have(self):
+        return self.lib.ref_bt_have(self.h)
+
+    def hann(self):
+        return np.ctypeslib.as_array(self.lib.ref_bt_hann(self.h), shape=(self.win,)).copy()
+
+    def inbuf(self):
+        return np.ctypeslib.as_array(self.lib.ref_bt_inbuf(self.h), shape=(self.win,)).copy()
+
+    def outbuf(self):
+        return np.ctypeslib.as_array(self.lib.ref_bt_outbuf(self.h), shape=(self.macro + self.half,)).copy()
+
+    def s16_to_float(self, v):
+        v = np.ascontiguousarray(v, np.int16).reshape(-1)
+        out = np.empty(v.size, np.float32)
+        self.lib.ref_bt_s16_to_float(v, out, v.size)
+        return out
+
+    def float_to_s16(self, v):
+        v = np.ascontiguousarray(v, np.float32).reshape(-1)
+        out = np.empty(v.size, np.int16)
+        self.lib.ref_bt_float_to_s16(v, out, v.size)
+        return out
+
+    def coef(self, row):
+        """Spectrum of cached hop `row` (below have()): [win/2 + 1] complex64."""
+        out = np.empty(self.win + 2, np.float32)
+        self.lib.ref_bt_coef(self.h, row, out)
+        return out.view(np.complex64)
+
+    def core(self, coef):
+        """The static blockThreshold_core / blockThreshold_adaptive_block on caller-supplied spectra (OracleBt.core)."""
+        return _bt_core_call(self.lib.ref_bt_core, self.h, self.win, coef)
 
 
 # ------------------------------------------------------------------------- AEC

@@ -1,12 +1,14 @@
 """GPU parity suite for BlockThresholding (-m gpu): HIP kernels through the C-ABI vs the oracle.
-Bar: bit-exact (same float operations in the same order; PARITY UNPINNED vs the reference itself,
-which cannot be built -- see oracle/bt_oracle.c)."""
+Bar: bit-exact (same float operations in the same order).  The oracle itself is held bitwise to the reference's
+audioDenoiseBlockTreshold.c compiled in place (tests/test_bt_oracle.py; everything but kiss_fft, which is held to
+numpy), and tests/test_bt_ref_gpu.py holds the device to goldens written by that build."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from audiosignalprocess_amd.synth import bt_samples
+from tests.bt_runs import ANY_WINDOWS
 from tests.oracle_lib import OracleBt
 
 pytestmark = pytest.mark.gpu
@@ -118,11 +120,6 @@ def test_wide_segment_signals_bit_exact(bt):
     for s in range(4):
         assert np.array_equal(y[s], OracleBt(n).run(x[s])), s
     g.close()
-
-
-ANY_WINDOWS = [320, 480, 800, 960, 224, 136, 62, 1000, 1440, 1920, 2048, 552]  # 20 / 30 / 50 / 60 ms at 16 kHz,
-# 10 / 20 / 30 / 40 ms at 48 kHz, lengths whose half has the prime factors 7, 17, 31 (generic butterfly) or is
-# odd / 4 5^3, the longest window the LDS tiles hold, and the 552 points of the reference's unittest_real_fft.cpp:22
 
 
 @pytest.mark.parametrize("n", ANY_WINDOWS)

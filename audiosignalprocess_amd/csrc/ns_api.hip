@@ -34,6 +34,9 @@ hipError_t launch_ns_frame1_flow(bool io16, float* state, int32_t* hist, const N
                                  unsigned* seq, unsigned* abort_w, unsigned want, int steps, int walk, int slot0,
                                  int ring, size_t per, int steady_on, unsigned long long* stamps = nullptr,
                                  unsigned* step_counts = nullptr);
+hipError_t launch_ns_frame1_list(bool io16, float* state, int32_t* hist, const NsTables* T, const float* in, float* out,
+                                 hipStream_t s, const int32_t* streams, const int32_t* counts, int n, int frame0,
+                                 size_t per, int steady_on);
 hipError_t launch_ns_frame2(bool io16, float* state, int32_t* hist, const NsTables* T,
                             const float* in, float* out, int num_streams, hipStream_t s,
                             unsigned long long* stamps = nullptr);
@@ -622,6 +625,19 @@ struct AspNsBatch {
   float* hb_tail = nullptr;    // [S][2][96]: dataBufHB[b][160..255]
   int32_t* hb_live = nullptr;  // [S]: energy1 != 0 of the frame being processed
   float* hb_stage = nullptr;   // host-memory callers: [2][num_high][S][160]
+  // List calls (AspNsBatch_AnalyzeProcessList): the batch's own copies of a call's lists.  A ring of kListSlots slots
+  // of 2 S words each ([streams | counts]), in pinned host memory and on the device: a call fills the next host slot,
+  // copies it to the device slot on the batch's stream and records the slot's event behind its last launch.  A slot
+  // is taken again only after that event, so every call enqueued back to back sees its own list, and the caller's
+  // arrays are free when the call returns.
+  static constexpr int kListSlots = 8;
+  int32_t* list_host = nullptr;
+  int32_t* list_dev = nullptr;
+  hipEvent_t list_ev[kListSlots] = {};
+  bool list_busy[kListSlots] = {};
+  int list_next = 0;
+  char* list_bounce = nullptr;  // pinned: a host-memory list call's staged output, before its live rows go to the caller
+  size_t list_bounce_cap = 0;
 };
 
 namespace {
@@ -718,6 +734,11 @@ int AspNsBatch_Free(AspNsBatch* b) {
   if (b->hb_tail) (void)hipFree(b->hb_tail);
   if (b->hb_live) (void)hipFree(b->hb_live);
   if (b->hb_stage) (void)hipFree(b->hb_stage);
+  if (b->list_host) (void)hipHostFree(b->list_host);
+  if (b->list_dev) (void)hipFree(b->list_dev);
+  if (b->list_bounce) (void)hipHostFree(b->list_bounce);
+  for (int i = 0; i < AspNsBatch::kListSlots; ++i)
+    if (b->list_ev[i]) (void)hipEventDestroy(b->list_ev[i]);
   if (b->ev0) (void)hipEventDestroy(b->ev0);
   if (b->ev1) (void)hipEventDestroy(b->ev1);
   for (int p = 0; p < 4; ++p) {
@@ -1250,6 +1271,131 @@ int AspNsBatch_AnalyzeProcessS16(AspNsBatch* b, const int16_t* in, int16_t* out,
     return flow_check(b);
   }
   return ASP_OK;
+}
+
+// The next slot of the batch's list ring, free for reuse: the launches that read it last have finished.
+static int list_slot_take(AspNsBatch* b, int* slot) {
+  const size_t words = (size_t)AspNsBatch::kListSlots * 2 * (size_t)b->S;
+  if (!b->list_host) HIP_TRY(hipHostMalloc((void**)&b->list_host, words * sizeof(int32_t), hipHostMallocDefault));
+  if (!b->list_dev) HIP_TRY(hipMalloc((void**)&b->list_dev, words * sizeof(int32_t)));
+  const int k = b->list_next;
+  if (!b->list_ev[k]) HIP_TRY(hipEventCreateWithFlags(&b->list_ev[k], hipEventDisableTiming));
+  if (b->list_busy[k]) {
+    HIP_TRY(hipEventSynchronize(b->list_ev[k]));
+    b->list_busy[k] = false;
+  }
+  *slot = k;
+  return ASP_OK;
+}
+
+// Fused Analyze+Process of the listed streams, ragged frame counts (asp_ns.h).  `in` / `out` are float or int16
+// frames (io16).  Everything is validated before anything is enqueued or allocated.
+static int list_run(AspNsBatch* b, const char* who, const int32_t* streams, const int32_t* counts, int n, const void* in,
+                    void* out, int max_frames, int mem, bool io16) {
+  AspDeviceScope dev_scope_;
+  int rc = check(b, dev_scope_);
+  if (rc) return rc;
+  char msg[160];
+#define LIST_FAIL(code, text)                          \
+  do {                                                 \
+    snprintf(msg, sizeof msg, "%s: %s", who, text);    \
+    return fail(code, msg);                            \
+  } while (0)
+  if (n < 0 || n > b->S) LIST_FAIL(ASP_ERR_PARAM, "n must be 0 .. num_streams");
+  if (max_frames < 0) LIST_FAIL(ASP_ERR_PARAM, "max_frames must not be negative");
+  if (mem != ASP_MEM_HOST && mem != ASP_MEM_DEVICE) LIST_FAIL(ASP_ERR_PARAM, "mem must be ASP_MEM_HOST or ASP_MEM_DEVICE");
+  if ((!in || !out) && n > 0 && max_frames > 0) LIST_FAIL(ASP_ERR_PARAM, "null frames");
+  if (n > 0 && !streams) LIST_FAIL(ASP_ERR_PARAM, "null stream list");
+  std::vector<unsigned char> seen((size_t)b->S, 0);
+  int maxc = 0;  // the longest entry
+  for (int i = 0; i < n; ++i) {
+    const int s = streams[i];
+    if (s < 0 || s >= b->S) LIST_FAIL(ASP_ERR_PARAM, "a listed stream is outside the batch");
+    if (seen[s]) LIST_FAIL(ASP_ERR_PARAM, "a stream is listed twice (two waves on one state would race)");
+    seen[s] = 1;
+    const int c = counts ? counts[i] : max_frames;
+    if (c < 0 || c > max_frames) LIST_FAIL(ASP_ERR_PARAM, "a count is outside 0 .. max_frames");
+    if (c > maxc) maxc = c;
+  }
+  if (b->fs != 16000)
+    LIST_FAIL(ASP_ERR_STATE, "list calls serve the one-band 16 kHz geometry only (the batch was initialised at 8, 32 or 48 kHz)");
+  if (b->kernel == 1 || b->kernel == 2)
+    LIST_FAIL(ASP_ERR_STATE, "SetKernel 1 / 2 is on: their sums associate differently from the list form's (SetKernel 0 or 3)");
+  if (!b->paired) LIST_FAIL(ASP_ERR_STATE, "needs streams driven only through the fused step (the batch is unpaired)");
+  if (b->step_counts || b->timeline || b->flow_stamps)
+    LIST_FAIL(ASP_ERR_STATE, "a diagnostic of the pair-layout kernel (step counts, timeline, stamps) is on: switch it off first");
+#undef LIST_FAIL
+  if (n == 0 || max_frames == 0 || maxc == 0) return ASP_OK;
+
+  const size_t esz = io16 ? sizeof(int16_t) : sizeof(float);
+  const size_t frame_bytes = (size_t)n * kBlockL * esz;  // one frame of the n rows
+  const size_t per = frame_bytes / sizeof(float);         // in float units, as the kernels count
+  const char* din = (const char*)in;
+  char* dout = (char*)out;
+  if (mem == ASP_MEM_HOST) {
+    rc = ensure_stage(b, (size_t)maxc);  // (n <= S rows per frame)
+    if (rc) return rc;
+  }
+  int slot = 0;
+  rc = list_slot_take(b, &slot);
+  if (rc) return rc;
+  int32_t* hl = b->list_host + (size_t)slot * 2 * b->S;
+  int32_t* dl = b->list_dev + (size_t)slot * 2 * b->S;
+  for (int i = 0; i < n; ++i) {
+    hl[i] = streams[i];
+    hl[n + i] = counts ? counts[i] : max_frames;
+  }
+  HIP_TRY(hipMemcpyAsync(dl, hl, (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+  b->list_busy[slot] = true;  // (from here on the slot's event is recorded, whatever fails below)
+  b->list_next = (slot + 1) % AspNsBatch::kListSlots;
+  hipError_t e = hipSuccess;
+  if (mem == ASP_MEM_HOST) {
+    e = hipMemcpyAsync(b->stage_in.p, in, frame_bytes * maxc, hipMemcpyHostToDevice, b->stream);
+    din = (const char*)b->stage_in.p;
+    dout = (char*)b->stage_out.p;
+  }
+  // launches of at most kHandoffMaxSteps frames of each entry, in stream order
+  for (int f0 = 0; f0 < maxc && e == hipSuccess; f0 += kHandoffMaxSteps)
+    e = launch_ns_frame1_list(io16, b->state, b->hist, b->tables, (const float*)(din + frame_bytes * f0),
+                              (float*)(dout + frame_bytes * f0), b->stream, dl, dl + n, n, f0, per, steady_arg(b));
+  const hipError_t er = hipEventRecord(b->list_ev[slot], b->stream);
+  if (e == hipSuccess) e = er;
+  if (e != hipSuccess) return fail(ASP_ERR_HIP, "enqueuing a list call", e);
+  if (mem != ASP_MEM_HOST) return ASP_OK;
+  // only rows and frames below counts[i] of the caller's `out` may change
+  if (!counts) {
+    HIP_TRY(hipMemcpyAsync(out, b->stage_out.p, frame_bytes * maxc, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+  } else {
+    // through the batch's pinned bounce buffer (it grows to the largest call), then the live rows only
+    const size_t bytes = frame_bytes * maxc;
+    if (b->list_bounce_cap < bytes) {
+      if (b->list_bounce) (void)hipHostFree(b->list_bounce);
+      b->list_bounce = nullptr;
+      b->list_bounce_cap = 0;
+      HIP_TRY(hipHostMalloc((void**)&b->list_bounce, bytes, hipHostMallocDefault));
+      b->list_bounce_cap = bytes;
+    }
+    HIP_TRY(hipMemcpyAsync(b->list_bounce, b->stage_out.p, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    const size_t row_bytes = (size_t)kBlockL * esz;
+    for (int i = 0; i < n; ++i)
+      for (int f = 0; f < counts[i]; ++f) {
+        const size_t off = frame_bytes * f + row_bytes * i;
+        memcpy((char*)out + off, b->list_bounce + off, row_bytes);
+      }
+  }
+  return flow_check(b);
+}
+
+int AspNsBatch_AnalyzeProcessList(AspNsBatch* b, const int32_t* streams, const int32_t* counts, int n, const float* in,
+                                  float* out, int max_frames, int mem) {
+  return list_run(b, "AnalyzeProcessList", streams, counts, n, in, out, max_frames, mem, false);
+}
+
+int AspNsBatch_AnalyzeProcessListS16(AspNsBatch* b, const int32_t* streams, const int32_t* counts, int n,
+                                     const int16_t* in, int16_t* out, int max_frames, int mem) {
+  return list_run(b, "AnalyzeProcessListS16", streams, counts, n, in, out, max_frames, mem, true);
 }
 
 int AspNsBatch_AnalyzeProcessReplay(AspNsBatch* b, const float* in, float* out, int frames_in_ring,

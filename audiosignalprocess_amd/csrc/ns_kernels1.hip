@@ -106,6 +106,23 @@ struct NsFlowArgs {
   unsigned walk;      // steps per chunk (grid y = ceil(steps / walk))
 };
 
+// ---- the list form (LIST, on the hand-off body): the launch steps SOME streams of the batch, each by its own number of
+// frames.  Wave w of the grid takes list entry w: its stream is streams[w], its frames are row w of `in` / `out`
+// ([frame][n][160]: NsFlowArgs::per = n rows), and its walk is its own min(kHandoffMaxSteps, counts[w] - frame0) steps:
+// one copy-in of the image, the steps, one hist_flush, one write-back.  No workgroup of the launch touches the state of
+// another one's streams (the host refuses a list that names a stream twice), so nothing is handed over inside the launch:
+// the list form neither polls nor publishes seq[] and never reads the abort word -- it has no spin loop -- and stream
+// order between launches is all the ordering it needs.  seq[] stays what the lock-step hand-off launches left, so those
+// go on before and after.  The state accesses stay sc1 and the image, the scalar row and the deferred histogram adds are
+// the hand-off body's; of NsFlowArgs only `per` is read.
+struct NsListArgs {
+  const int32_t* streams;  // [n] stream of entry i: distinct, inside the batch (checked by the host)
+  const int32_t* counts;   // [n] frames of entry i in the whole call
+  int n;                   // entries (>= 1); waves past them exit behind the workgroup's barrier, as do entries with no step
+  int frame0;              // frames of the call in front of this launch (`in` / `out` point at frame frame0)
+};
+constexpr int kListMaxSteps = 64;  // steps of an entry per launch (the host's kHandoffMaxSteps)
+
 // The frame's new samples: 4 consecutive ones from sample `idx` of `in` (int16 frames: converted).
 template <bool IO16>
 __device__ __forceinline__ float4 load_frame4(const float* in, size_t idx) {
@@ -303,11 +320,14 @@ struct NsDiagArgs {
 // The frame step.  DIAG: the diagnostic stamps and the per-stream step counts exist (ns_frame1_diag_kernel); the
 // product kernels (ns_frame1_kernel) are the DIAG = false instantiations, where NS_STAMP expands to nothing.
 // steady_on: 0 routes every step through the generic body (AspNsBatch_SetSteady, A / B runs and tests).
-template <bool IO16, bool FLOW, bool DIAG>
+// LIST: the list form of the hand-off body (NsListArgs; ns_list1_kernel); everything it changes is under `if constexpr`.
+template <bool IO16, bool FLOW, bool DIAG, bool LIST = false>
 __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t* __restrict__ hist_all,
                                               const NsTables* __restrict__ T, const float* __restrict__ in,
                                               float* __restrict__ out, int num_streams, int steady_on,
-                                              const NsFlowArgs& fa, const NsDiagArgs& dg) {
+                                              const NsFlowArgs& fa, const NsDiagArgs& dg,
+                                              [[maybe_unused]] const NsListArgs& la = NsListArgs{nullptr, nullptr, 0, 0}) {
+  static_assert(!LIST || (FLOW && !DIAG), "the list form exists on the hand-off body's product kernels");
   // the diagnostic buffer (the hand-off build parks its address in a vector register pair: ns_in_vgpr)
   [[maybe_unused]] const unsigned long long diag_buf =
       DIAG ? (FLOW ? ns_in_vgpr((unsigned long long)dg.buf) : (unsigned long long)dg.buf) : 0ull;
@@ -362,7 +382,9 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
   // most 64 steps), added to the stream's two counts when the wave is done
   [[maybe_unused]] unsigned diag_steps = 0;
   [[maybe_unused]] constexpr int ns_body_tag = 0;  // (budget build: the marks outside the two bodies)
-  if constexpr (FLOW) {
+  if constexpr (LIST) {
+    // the wave's walk is steps 0 .. (its count) - 1 of the launch's slice, frame j in slot j: set where the entry is read
+  } else if constexpr (FLOW) {
     flow_j = blockIdx.y * fa.walk;
     flow_end = flow_j + fa.walk < fa.steps ? flow_j + fa.walk : fa.steps;
     flow_slot = ((unsigned)fa.slot0 + flow_j) % (unsigned)fa.ring;
@@ -402,9 +424,20 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
   const uint32_t gmask = g ? 0x80000000u : 0u;
   const int stream_raw = blockIdx.x * 4 + wv;
   bool wave_live = stream_raw < num_streams;
+  // `stream` is the wave's row of a frame of `in` / `out` and, but for the list form, the index of its state block
+  // (list form: the wave's list entry; the kernel passes the list's length as num_streams)
   const int stream = wave_live ? stream_raw : num_streams - 1;  // clamped for the loads
-  float* __restrict__ st = state + (size_t)stream * kStreamDwords;
-  int32_t* __restrict__ hist = hist_all + (size_t)stream * kHistDwords;
+  [[maybe_unused]] int list_stream = 0;
+  if constexpr (LIST) {
+    // the entry's words: wave-uniform scalar loads of what the host wrote before the launch
+    const int left = la.counts[stream] - la.frame0;
+    flow_end = left < 0 ? 0u : (left > kListMaxSteps ? (unsigned)kListMaxSteps : (unsigned)left);
+    wave_live = wave_live && flow_end != 0u;
+    list_stream = la.streams[stream];
+  }
+  const int state_ix = LIST ? list_stream : stream;
+  float* __restrict__ st = state + (size_t)state_ix * kStreamDwords;
+  int32_t* __restrict__ hist = hist_all + (size_t)state_ix * kHistDwords;
   const StateAcc<FLOW> sa(st, FLOW ? imgs[wv] : nullptr);
   float* outj = out;  // this step's frame of `out` (hand-off build: its ring slot)
   auto diag_flush_steps = [&]() __attribute__((always_inline)) {
@@ -495,8 +528,10 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
   };
   [[maybe_unused]] float4 img_v[FLOW ? kImgVec4 : 1];
   if constexpr (FLOW) {
-    flow_load_in(flow_slot);
-    if (wave_live) wave_live = handoff_wait(fa.hand, fa.want + flow_j, stream, lane);
+    // (list form: an entry without a step reads no frame, and there is nothing to wait for: NsListArgs)
+    if (!LIST || wave_live) flow_load_in(flow_slot);
+    if constexpr (!LIST)
+      if (wave_live) wave_live = handoff_wait(fa.hand, fa.want + flow_j, stream, lane);
     if (wave_live) sa.image_request(lane, img_v);  // the copy-in: in flight behind the table staging
   } else {
     sv = st[kOffScalars + lane];
@@ -562,7 +597,8 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
   // the frame of the chunk's next step is requested while this step still has its inverse transform ahead
 #define NS_NEXT_FRAME()                                                                        \
   if constexpr (FLOW) {                                                                        \
-    flow_slot = flow_slot + 1u == (unsigned)fa.ring ? 0u : flow_slot + 1u;                     \
+    if constexpr (LIST) flow_slot = flow_slot + 1u; /* (frame j + 1 of the slice; requested only below the count) */ \
+    else flow_slot = flow_slot + 1u == (unsigned)fa.ring ? 0u : flow_slot + 1u;                \
     if (flow_j + 1u < flow_end) flow_load_in(flow_slot);                                       \
   }
   // the step is done for this stream.  Hand-off build: after the walk's last step the wave writes its image back,
@@ -585,7 +621,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
     if (walk_done_) {                                                                          \
       NS_BUDGET_ASIDE()                                                                        \
       diag_flush_steps();                                                                      \
-      if (lane == 0) handoff_publish(fa.hand.seq + stream, fa.want + flow_j);                  \
+      if (!LIST && lane == 0) handoff_publish(fa.hand.seq + stream, fa.want + flow_j);         \
       return;                                                                                  \
     }                                                                                          \
     ++flow_j;                                                                                  \
@@ -1099,7 +1135,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       if constexpr (STEADY && DEFER) {
         // the steady body adds in every step (updateParsFlag >= 1, mup3 > 2) and closes no window: the three features
         // as they stand here go into the step's slot, from lane 0; hist_flush() counts them
-        const unsigned rel = flow_j - blockIdx.y * fa.walk;  // the step of the walk
+        const unsigned rel = LIST ? flow_j : flow_j - blockIdx.y * fa.walk;  // the step of the walk
         // (past the walk's first kPendSteps steps a slot may be taken -- which ones depends on the zero-energy and
         // generic steps behind -- so every record counts what is pending first; the product's walks are 4 and 8 steps)
         if (rel >= (unsigned)kPendSteps) hist_flush();
@@ -1451,6 +1487,15 @@ __global__ __launch_bounds__(256, 4) void ns_frame1_kernel(float* __restrict__ s
   ns_frame1_run<IO16, FLOW, false>(state, hist_all, T, in, out, num_streams, steady_on, fa, NsDiagArgs{nullptr, 0});
 }
 
+// the list kernels (NsListArgs): the hand-off body's product step on the listed streams, float and int16 frames
+template <bool IO16>
+__global__ __launch_bounds__(256, 4) void ns_list1_kernel(float* __restrict__ state, int32_t* __restrict__ hist_all,
+                                                          const NsTables* __restrict__ T,
+                                                          const float* __restrict__ in, float* __restrict__ out,
+                                                          int steady_on, NsFlowArgs fa, NsListArgs la) {
+  ns_frame1_run<IO16, true, false, true>(state, hist_all, T, in, out, la.n, steady_on, fa, NsDiagArgs{nullptr, 0}, la);
+}
+
 // the diagnostic kernels (stamps, timeline, step counts): float frames only, which is what their entry points use
 template <bool FLOW>
 __global__ __launch_bounds__(256, 4) void ns_frame1_diag_kernel(float* __restrict__ state,
@@ -1622,6 +1667,22 @@ hipError_t launch_ns_frame1_flow(bool io16, float* state, int32_t* hist, const N
   else
     hipLaunchKernelGGL((ns_frame1_kernel<false, true>), grid, block, 0, s, state, hist, T, in, out,
                        num_streams, steady_on, fa);
+  return hipGetLastError();
+}
+
+// The list form: entry i of the n listed streams advances by min(kListMaxSteps, max(0, counts[i] - frame0)) frames;
+// in / out point at frame frame0 of [frame][n][160] (`per` floats between two frames); streams / counts: device.
+hipError_t launch_ns_frame1_list(bool io16, float* state, int32_t* hist, const NsTables* T, const float* in, float* out,
+                                 hipStream_t s, const int32_t* streams, const int32_t* counts, int n,
+                                 int frame0, size_t per, int steady_on) {
+  if (n < 1) return hipErrorInvalidValue;
+  const dim3 grid((n + 3) / 4), block(256);
+  const NsFlowArgs fa = {{nullptr, nullptr}, 0u, 0, 1, (unsigned)per, (unsigned)kListMaxSteps, (unsigned)kListMaxSteps};
+  const NsListArgs la = {streams, counts, n, frame0};
+  if (io16)
+    hipLaunchKernelGGL((ns_list1_kernel<true>), grid, block, 0, s, state, hist, T, in, out, steady_on, fa, la);
+  else
+    hipLaunchKernelGGL((ns_list1_kernel<false>), grid, block, 0, s, state, hist, T, in, out, steady_on, fa, la);
   return hipGetLastError();
 }
 

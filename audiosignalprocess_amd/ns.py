@@ -60,6 +60,8 @@ def load_library():
         "AspNsBatch_Process": [vp, vp, vp, ip],
         "AspNsBatch_AnalyzeProcess": [vp, vp, vp, ip, ip],
         "AspNsBatch_AnalyzeProcessS16": [vp, vp, vp, ip, ip],
+        "AspNsBatch_AnalyzeProcessList": [vp, vp, vp, ip, vp, vp, ip, ip],
+        "AspNsBatch_AnalyzeProcessListS16": [vp, vp, vp, ip, vp, vp, ip, ip],
         "AspNsBatch_AnalyzeProcessBands": [vp, vp, vp, vp, vp, ip, ip],
         "AspNsBatch_ProcessBands": [vp, vp, vp, vp, vp, ip],
         "AspNsBatch_num_bands": [vp],
@@ -254,6 +256,42 @@ class NsBatch:
         _check(self.lib.AspNsBatch_AnalyzeProcessS16(self.h, _ptr(pcm), _ptr(out), F, MEM_HOST),
                "AspNsBatch_AnalyzeProcessS16")
         return out
+
+    # -- some streams of the batch, ragged frame counts (include/asp_ns.h, AspNsBatch_AnalyzeProcessList)
+    @staticmethod
+    def _lists(streams, counts):
+        streams = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+            assert counts.shape == streams.shape
+        return streams, counts
+
+    def analyze_process_list(self, streams, counts, frames, out=None):
+        """List entry i is stream streams[i] and advances by counts[i] frames (counts None: all of them); frames
+        [max_frames][n][160] float32 or int16, row i = entry i -> `out` (default: a copy of `frames`), in which frame f
+        of row i is the denoised frame where f < counts[i] and left as it was elsewhere."""
+        frames = np.ascontiguousarray(frames)
+        assert frames.dtype in (np.float32, np.int16), frames.dtype
+        streams, counts = self._lists(streams, counts)
+        F, n = frames.shape[0], streams.shape[0]
+        assert frames.shape == (F, n, BLOCKL)
+        if out is None:
+            out = frames.copy()
+        assert out.shape == frames.shape and out.dtype == frames.dtype and out.flags.c_contiguous
+        s16 = frames.dtype == np.int16
+        fn = self.lib.AspNsBatch_AnalyzeProcessListS16 if s16 else self.lib.AspNsBatch_AnalyzeProcessList
+        _check(fn(self.h, _ptr(streams), _ptr(counts) if counts is not None else None, n, _ptr(frames), _ptr(out), F,
+                  MEM_HOST), "AspNsBatch_AnalyzeProcessList" + ("S16" if s16 else ""))
+        return out
+
+    def analyze_process_list_device(self, streams, counts, in_ptr, out_ptr, max_frames, s16=False):
+        """The same on device buffers [max_frames][n][160] (asynchronous on the batch's stream); streams / counts are
+        host arrays, free for reuse when the call returns."""
+        streams, counts = self._lists(streams, counts)
+        fn = self.lib.AspNsBatch_AnalyzeProcessListS16 if s16 else self.lib.AspNsBatch_AnalyzeProcessList
+        _check(fn(self.h, _ptr(streams), _ptr(counts) if counts is not None else None, streams.shape[0],
+                  C.c_void_p(in_ptr), C.c_void_p(out_ptr), max_frames, MEM_DEVICE),
+               "AspNsBatch_AnalyzeProcessList" + ("S16" if s16 else ""))
 
     # -- device-pointer path (asynchronous on the batch's stream)
     def analyze_process_device(self, in_ptr, out_ptr, num_frames):

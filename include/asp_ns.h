@@ -170,6 +170,33 @@ int AspNsBatch_ImportHbState(AspNsBatch* b, int stream, const AspNsHbState* in);
 int AspNsBatch_AnalyzeProcessS16(AspNsBatch* b, const int16_t* in, int16_t* out,
                                  int num_frames, int mem);
 
+/* Fused Analyze+Process of SOME streams of the batch: list entry i is stream streams[i], which advances by
+ * counts[i] frames (counts == NULL: max_frames each).  in / out: [max_frames][n][160], row i = entry i;
+ * frame f of row i is used iff f < counts[i]; the rest of out is not written; in == out allowed.
+ * Streams not listed, and entries with count 0, are untouched: state, histograms, everything.
+ * What a jitter buffer needs: at one tick some streams have no frame, most have one, some a burst of two or three.
+ * Results are bit for bit those of the lock-step calls fed the same frames per stream.
+ *   - streams / counts are HOST arrays, free for reuse when the call returns (also for ASP_MEM_DEVICE, where the call
+ *     stays asynchronous on the batch's stream: the batch keeps its own copy of each call's lists, in a ring of 8
+ *     slots.  Up to 8 list calls may be in flight; a further call BLOCKS the host until the call 8 before it has
+ *     finished on the device, then enqueues as usual);
+ *   - mem applies to the frames; ASP_MEM_HOST copies in and out, returns when done, and changes only rows and frames
+ *     below counts[i] of out;
+ *   - max_frames may exceed 64: the call is cut into launches of at most 64 frames of each entry, in stream order;
+ *     n == 0 or max_frames == 0 is ASP_OK and enqueues nothing;
+ *   - refused before anything is enqueued, the batch left as it was (AspNs_last_error has the reason):
+ *     ASP_ERR_PARAM for a null pointer, n outside 0 .. num_streams, a stream outside the batch or listed twice, a
+ *     count outside 0 .. max_frames, a bad mem; ASP_ERR_STATE for a batch that is not initialised or not at 16 kHz
+ *     (this is the one-band 16 kHz geometry: no 8 kHz, no 32 / 48 kHz bands), after SetKernel 1 or 2 (their sums
+ *     associate differently), after a two-call Analyze / Process (unpaired streams), or while a diagnostic of the
+ *     pair-layout kernel (step counts, timeline, stamps) is on;
+ *   - there is one form: SetFlow, SetFlowWalk, SetSplit and SetGraph do not affect it (SetSteady does), and it
+ *     leaves the hand-off build's step counters alone, so lock-step calls go on before and after. */
+int AspNsBatch_AnalyzeProcessList(AspNsBatch* b, const int32_t* streams, const int32_t* counts, int n,
+                                  const float* in, float* out, int max_frames, int mem);
+int AspNsBatch_AnalyzeProcessListS16(AspNsBatch* b, const int32_t* streams, const int32_t* counts, int n,
+                                     const int16_t* in, int16_t* out, int max_frames, int mem);
+
 int AspNsBatch_ExportState(AspNsBatch* b, int stream, AspNsState* out);
 int AspNsBatch_ImportState(AspNsBatch* b, int stream, const AspNsState* in);
 /* priorSpeechProb of every stream (noise_suppression.c:57-66), out[num_streams]. */

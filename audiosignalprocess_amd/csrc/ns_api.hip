@@ -59,6 +59,8 @@ hipError_t launch_debug_tanh_wave(unsigned start, unsigned count, unsigned* n_ba
 hipError_t launch_debug_guards_wave(unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits, hipStream_t s);
 hipError_t launch_debug_fallbacks_wave(int what, unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits,
                                        const NsTables* T, hipStream_t s);
+hipError_t launch_debug_shortdiv_wave(int what, unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits,
+                                      const NsTables* T, hipStream_t s);
 hipError_t launch_debug_compare(int fn_a, int fn_b, unsigned start, unsigned count,
                                 unsigned* n_bad, unsigned* bad_bits, float param,
                                 const NsTables* T, hipStream_t s);
@@ -1830,6 +1832,8 @@ int AspNs_debug_compare(int fn_a, int fn_b, uint32_t start, uint32_t count, uint
         : fn_a == 24 ? launch_debug_guards_wave(start, count, d, d + 1, nullptr)
         // (fn 25: the steady step's wave-level libm fallbacks and reciprocal chain; fn_b chooses what is swept, 0 .. 5)
         : fn_a == 25 ? launch_debug_fallbacks_wave(fn_b, start, count, d, d + 1, T, nullptr)
+        // (fn 26: the steady step's short division chains beside the forms they replace; fn_b chooses what is swept)
+        : fn_a == 26 ? launch_debug_shortdiv_wave(fn_b, start, count, d, d + 1, T, nullptr)
                      : launch_debug_compare(fn_a, fn_b, start, count, d, d + 1, param, T, nullptr);
   unsigned h[65];
   if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);

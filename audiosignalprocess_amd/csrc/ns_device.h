@@ -173,6 +173,47 @@ __device__ __forceinline__ f32x2 frcp2(f32x2 d) {  // frcp for two, packed
   const f32x2 e1 = __builtin_elementwise_fma(-d, r1, one);
   return __builtin_elementwise_fma(e1, r1, r1);
 }
+// Shorter chains for quotients whose operands are NOT two free floats: with one free 32-bit pattern the quotient is a
+// function of that pattern alone, and an exhaustive sweep decides whether a chain equals fdiv's there.  Each form is
+// proved on the CPU for every v_rcp_f32 result within an ulp of the rounded reciprocal (tools/probe/ns_shortdiv_sweep.c,
+// profiles/r16_ns_shortdiv_sweep.txt) and swept on the device against fdiv at its call site's arguments
+// (tests/test_ns_shortdiv_gpu.py).  Neither is a general division: fdiv / fdiv2 keep every call with two free operands.
+//   fdiv_c: c / d for a constant numerator -- the seed reciprocal serves both corrections, the refinement (e0, r1) is
+//           dropped: five steps behind the v_rcp_f32 instead of seven, and a shorter chain behind it.  Proved for
+//           c = 40 and every d in [1, 2^127).
+//   fdiv_1c: n / d with ONE correction (no e2, q2), the refined reciprocal kept.  Proved for
+//           (1 - p) / (p + 0.0001f) at every p in [0.01, 1].
+__device__ __forceinline__ float fdiv_c(float c, float d) {
+  const float r0 = __builtin_amdgcn_rcpf(d);
+  const float q0 = c * r0;
+  const float e1 = __builtin_fmaf(-d, q0, c);
+  const float q1 = __builtin_fmaf(e1, r0, q0);
+  const float e2 = __builtin_fmaf(-d, q1, c);
+  return __builtin_fmaf(e2, r0, q1);
+}
+__device__ __forceinline__ f32x2 fdiv2_c(float c, f32x2 d) {
+  f32x2 r0;
+  r0.x = __builtin_amdgcn_rcpf(d.x);
+  r0.y = __builtin_amdgcn_rcpf(d.y);
+  const f32x2 n = {c, c};
+  const f32x2 q0 = n * r0;
+  const f32x2 e1 = __builtin_elementwise_fma(-d, q0, n);
+  const f32x2 q1 = __builtin_elementwise_fma(e1, r0, q0);
+  const f32x2 e2 = __builtin_elementwise_fma(-d, q1, n);
+  return __builtin_elementwise_fma(e2, r0, q1);
+}
+__device__ __forceinline__ float fdiv_1c(float n, float d) {
+  const float r1 = fdiv_rcp(d);
+  const float q0 = n * r1;
+  const float e1 = __builtin_fmaf(-d, q0, n);
+  return __builtin_fmaf(e1, r1, q0);
+}
+// a / d for two values and a divisor shared by the wave: div_by_uniform's three operations, packed
+__device__ __forceinline__ f32x2 div_by_uniform2(f32x2 a, float d, float rd) {
+  const f32x2 r = {rd, rd}, nd = {-d, -d};
+  const f32x2 q0 = a * r;
+  return __builtin_elementwise_fma(__builtin_elementwise_fma(nd, q0, a), r, q0);
+}
 // Three bins of a lane of the one-stream-per-wave kernel (two owned + bin 128) as one packed pair
 // and a scalar: +, -, * and fma on an F3 compile to v_pk_* for the pair.  Every operation is the IEEE
 // single operation of its scalar spelling (no contraction), so results are bit-identical to per-bin loops.
@@ -501,12 +542,22 @@ __device__ __forceinline__ float log_f32_via_f64(float x) {
 //   log x = k ln2 + log c + (r - r^2/2 + ... - r^6/6), truncation < 2^-50 of the result.
 // tab[i] = {invc, log c} is built on the host in long double (ns_api.hip).
 constexpr unsigned kLogOff = 0x3f328000u;
+// MAD (ns_kernels1.hip's calls; the other kernels' listings stay): the reduced argument's pattern, ix - (tmp &
+// 0xff800000), is ix - (k << 23) with the k that is formed anyway -- one v_mad_i32_i24(k, -2^23, ix), both factors within
+// 24 signed bits, instead of an AND and a subtract.  (Stated as an instruction: the compiler selects a shift and a
+// subtract.)  The same bits for every ix, so every value behind it is what it was.
+__device__ __forceinline__ unsigned log_reduced_bits_mad(int k, unsigned ix) {
+  unsigned z;
+  asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(z) : "v"(k), "s"(0xff800000u), "v"(ix));
+  return z;
+}
+template <bool MAD = false>
 __device__ __forceinline__ double log_tab_f64(float x, const double2* __restrict__ tab) {
   const unsigned ix = __float_as_uint(x);
   const unsigned tmp = ix - kLogOff;
   const int i = (tmp >> 16) & 127;
   const int k = (int)tmp >> 23;  // arithmetic
-  const double z = (double)__uint_as_float(ix - (tmp & 0xff800000u));
+  const double z = (double)__uint_as_float(MAD ? log_reduced_bits_mad(k, ix) : ix - (tmp & 0xff800000u));
   const double2 t = tab[i];
   const double r = __builtin_fma(z, t.x, -1.0);
   const double kd = (double)k;
@@ -539,7 +590,7 @@ __device__ __attribute__((noinline)) float log_f32_slow(float x) { return (float
 __device__ __attribute__((noinline)) float exp_f32_slow(float x) { return (float)exp((double)x); }
 __device__ __attribute__((noinline)) float sqrt_f32_slow(float x) { return sqrtf(x); }
 
-template <int N>
+template <int N, bool MAD = false>
 __device__ __forceinline__ void log_f32_via_tab_n(const float (&x)[N], float (&out)[N],
                                                   const double2* __restrict__ tab) {
   unsigned bad = 0;
@@ -549,7 +600,7 @@ __device__ __forceinline__ void log_f32_via_tab_n(const float (&x)[N], float (&o
     // nothing can fault) and is flagged: the fallback below recomputes the lane's values
     const unsigned ax = __float_as_uint(x[k]);
     const unsigned normal_pos = (ax - 0x00800000u) < 0x7f000000u ? 1u : 0u;  // [2^-126, inf)
-    const double y = log_tab_f64(x[k], tab);
+    const double y = log_tab_f64<MAD>(x[k], tab);
     bad |= (normal_pos ^ 1u) | (f64_rounds_safely_to_f32(y) ? 0u : 1u);
     out[k] = (float)y;
   }
@@ -600,7 +651,7 @@ __device__ __forceinline__ void log_f32_via_tab_n_wave(const float (&x)[N], floa
 #pragma unroll
   for (int k = 0; k < N; ++k) {
     bad |= lanes_not_positive_normal(x[k]);
-    const double y = log_tab_f64(x[k], tab);
+    const double y = log_tab_f64<true>(x[k], tab);
     bad |= __builtin_amdgcn_ballot_w64(f64_rounds_unsafely_to_f32(y));
     out[k] = (float)y;
   }
@@ -663,35 +714,45 @@ __device__ __forceinline__ void fsqrt_n(const float (&x)[N], float (&out)[N]) {
 // compiler rebuilds the mask of a class test through a select and a second compare.)  Behind the branch, where it is
 // free, a negative argument gets sqrtf's NaN -- fsqrt_n returns +inf for a negative subnormal, outside its contract
 // x >= 0 -- so this form equals sqrtf for EVERY float bit pattern (tests/test_ns_guards_gpu.py sweeps them on the
-// device).  The tiny-argument branch is fsqrt_n's.  fsqrt_n itself stays as it is: ns_kernels.hip and
+// device).  The tiny-argument case is found by ONE compare per argument, "below 2^-100", straight to a lane mask (zeros
+// and negative arguments are flagged with it); the masks are OR-ed as scalars and where some lane of the wave is flagged
+// fsqrt_n's exact per-lane test and its branch run, out of line.  fsqrt_n itself stays as it is: ns_kernels.hip and
 // ns_kernels2.hip use it.
 template <int N>
 __device__ __forceinline__ void fsqrt_n_wave(const float (&x)[N], float (&out)[N]) {
-  unsigned bad = 0;
+  unsigned long long tiny = 0;    // the wave's lanes with an argument below 2^-100 in some slot
   unsigned long long passes = 0;  // the wave's lanes with a result that is not finite in some slot
 #pragma unroll
   for (int k = 0; k < N; ++k) {
     const float xv = x[k];
+    // fsqrt_n's chain without its refinement of g and h (e and the two steps that use it): ONE correction of g = x r by
+    // the exact residual x - g g, scaled by h = r / 2.  With the v_rsq_f32 of this device that is fsqrt_n's value on
+    // every float in [2^-100, inf) -- a property of the instruction's results, not of every 1-ulp reciprocal square
+    // root (tools/probe/ns_shortdiv_sweep.c counts 566 arguments that fail for SOME seed within an ulp), so it is
+    // swept on the device in every test run: function 26 of AspNs_debug_compare against fsqrt, function 24 against
+    // sqrtf (tests/test_ns_shortdiv_gpu.py, tests/test_ns_guards_gpu.py).
     const float r = __builtin_amdgcn_rsqf(xv);
-    float g = xv * r;
-    float h = 0.5f * r;
-    const float e = __builtin_fmaf(-h, g, 0.5f);
-    g = __builtin_fmaf(g, e, g);
-    h = __builtin_fmaf(h, e, h);
+    const float g = xv * r;
+    const float h = 0.5f * r;
     const float d = __builtin_fmaf(-g, g, xv);
     out[k] = __builtin_fmaf(d, h, g);
     passes |= __builtin_amdgcn_ballot_w64(!(fabsf(out[k]) < __builtin_inff()));
-    bad |= (xv < 0x1p-100f && xv > 0.0f) ? 1u : 0u;
+    tiny |= __builtin_amdgcn_ballot_w64(xv < 0x1p-100f);
   }
   if (ASP_NS_RARE(passes != 0)) {
 #pragma unroll
     for (int k = 0; k < N; ++k)
       out[k] = (x[k] == 0.0f || x[k] == __builtin_inff()) ? x[k] : (x[k] < 0.0f ? __builtin_nanf("") : out[k]);
   }
-  if (ASP_NS_RARE(bad != 0)) {
+  if (ASP_NS_RARE(tiny != 0)) {
+    unsigned bad = 0;
 #pragma unroll
-    for (int k = 0; k < N; ++k)
-      if (x[k] < 0x1p-100f && x[k] > 0.0f) out[k] = sqrt_f32_slow(x[k]);
+    for (int k = 0; k < N; ++k) bad |= (x[k] < 0x1p-100f && x[k] > 0.0f) ? 1u : 0u;
+    if (bad != 0) {
+#pragma unroll
+      for (int k = 0; k < N; ++k)
+        if (x[k] < 0x1p-100f && x[k] > 0.0f) out[k] = sqrt_f32_slow(x[k]);
+    }
   }
 }
 __device__ __forceinline__ float fsqrt_wave(float x) {

@@ -885,14 +885,14 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
                                                            __float_as_int(cterm[2][j])))
         const float cntv = NS_LANES3_F(0), cnt1v = NS_LANES3_F(1), rcnt1v = NS_LANES3_F(2);  // rcnt1 == 1.f / cnt1
 #undef NS_LANES3_F
-        tracker_step1(lqT, denT, lmagn[2], cntv, cnt1v, rcnt1v);
+        tracker_step1_c(lqT, denT, lmagn[2], cntv, cnt1v, rcnt1v);
       }
 #pragma unroll
       for (int s = 0; s < 3; ++s) {
         {
           const float cnt = cterm[s][0], cnt1 = cterm[s][1], rcnt1 = cterm[s][2];
           f32x2 lq = {LQ[s][0], LQ[s][1]}, den = {DEN[s][0], DEN[s][1]};
-          tracker_step2(lq, den, f32x2{lmagn[0], lmagn[1]}, cnt, cnt1, rcnt1);
+          tracker_step2_c(lq, den, f32x2{lmagn[0], lmagn[1]}, cnt, cnt1, rcnt1);
           LQ[s][0] = lq.x; LQ[s][1] = lq.y;
           DEN[s][0] = den.x; DEN[s][1] = den.y;
         }
@@ -1036,8 +1036,11 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       // ---- ComputeSpectralDifference (ns_core.c:595-634)
       {
         float avgMagn = sumMagn;
-        avgPauseMean = DIV129(avgPauseMean);
-        avgMagn = DIV129(avgMagn);
+        {  // two independent wave-uniform quotients by the bin count: DIV129's three operations, packed
+          const f32x2 q = DIV129_2((f32x2{avgPauseMean, avgMagn}));
+          avgPauseMean = q.x;
+          avgMagn = q.y;
+        }
         float cv[NS3], vp[NS3], vm[NS3];
 #pragma unroll
         for (int k = 0; k < NS3; ++k) {
@@ -1051,8 +1054,11 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
         covMagnPause += cv[2];
         varPause += vp[2];
         varMagn += vm[2];
-        covMagnPause = DIV129(covMagnPause);
-        varPause = DIV129(varPause);
+        {
+          const f32x2 q = DIV129_2((f32x2{covMagnPause, varPause}));
+          covMagnPause = q.x;
+          varPause = q.y;
+        }
         varMagn = DIV129(varMagn);
         fd6 += signalEnergy;
         // (its two quotients are divided in phase 8, each beside another wave-uniform quotient that is independent of
@@ -1073,7 +1079,7 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
           float lt1p[2];
           // (the per-lane form: this is the step's widest point, and the wave-level form of these two chains costs the
           // hand-off product kernels three spilled vector registers, profiles/README.md)
-          log_f32_via_tab_n<2>(t1p, lt1p, logts);
+          log_f32_via_tab_n<2, true>(t1p, lt1p, logts);
           lt1[0] = lt1p[0]; lt1[1] = lt1p[1];
           lt1[2] = lt1_tail;
         } else {
@@ -1201,7 +1207,8 @@ __device__ __forceinline__ void ns_frame1_run(float* __restrict__ state, int32_t
       }
       float probSpeech[NS3];
       {
-        const float gainPrior = fdiv(1.f - priorSpeechProb, priorSpeechProb + 0.0001f);
+        // one free operand, priorSpeechProb in [0.01, 1] behind its clamps: the one-correction chain is fdiv's quotient
+        const float gainPrior = fdiv_1c(1.f - priorSpeechProb, priorSpeechProb + 0.0001f);
         {
           float pd[NS3];
 #pragma unroll
@@ -1600,9 +1607,86 @@ __global__ void debug_fallbacks_wave_kernel(int what, unsigned start, unsigned c
   }
 }
 
+// Test seam: the steady step's short division chains (ns_device.h: fdiv_c, fdiv_1c, div_by_uniform2; ns_step.h: fdiv40)
+// and the logarithm's one-instruction argument reduction, each beside the form it replaces, on every 32-bit pattern in
+// [start, start + count), 64 consecutive patterns to a wave; bits are compared, or NaN-ness on both sides.  `what`:
+//   0  fdiv40 and both halves of fdiv40_2 against fdiv(FACTOR, d), d = max(pattern, 1) as the trackers form it (+inf and
+//      NaNs included)
+//   1  gainPrior: the pattern as priorSpeechProb through ns_prior_update's clamps, then fdiv_1c against fdiv of
+//      (1 - p) / (p + 0.0001f)
+//   2  the logarithm: the pattern as the argument's bits through log_reduced_bits_mad against the AND and subtract, and
+//      log_f32_via_tab_n<1, true> against log_f32_via_tab
+//   3  both halves of div_by_uniform2 against div_by_uniform, divisor 129 (the bin count) and its rounded reciprocal
+//   4  fsqrt_wave (one correction of x r) against fsqrt (g and h refined first) on every pattern of a non-negative
+//      float or a NaN -- tiny arguments, zero and +inf through both forms' own branches
+// Candidates that do NOT ship (their counts are recorded, profiles/README.md; nothing in the step calls them):
+//   5  the phase-8 quotient tn / ((1 + tn) + 0.0001f), tn = 2 * pattern (snrLocPrior), fdiv_1c against fdiv
+//   6  fsqrt's chain with only h unrefined, for arguments in [2^-100, inf)
+__global__ void debug_shortdiv_wave_kernel(int what, unsigned start, unsigned count, unsigned* n_bad,
+                                           unsigned* bad_bits, const NsTables* __restrict__ T) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const unsigned bits = start + i;
+  const float x = __uint_as_float(bits);
+  auto eq = [](float a, float b) { return (__float_as_uint(a) == __float_as_uint(b)) || (a != a && b != b); };
+  bool same = true;
+  if (what == 0) {
+    const float d = fmax_raw(x, 1.0f), fac = NS_FACTOR * 1.f;
+    const float want = fdiv(fac, d);
+    const f32x2 a = fdiv40_2(f32x2{d, 1.5f}), b = fdiv40_2(f32x2{3.f, d});
+    same = eq(fdiv40(d), want) && eq(a.x, want) && eq(b.y, want) && eq(a.y, fdiv(fac, 1.5f)) && eq(b.x, fdiv(fac, 3.f));
+  } else if (what == 1) {
+    float p = x;
+    if (p > 1.f) p = 1.f;
+    if (p < 0.01f) p = 0.01f;
+    same = eq(fdiv_1c(1.f - p, p + 0.0001f), fdiv(1.f - p, p + 0.0001f));
+  } else if (what == 2) {
+    const unsigned tmp = bits - kLogOff;
+    same = log_reduced_bits_mad((int)tmp >> 23, bits) == bits - (tmp & 0xff800000u);
+    const double2* lt = reinterpret_cast<const double2*>(T->logtab);
+    const float in[1] = {x};
+    float o[1];
+    log_f32_via_tab_n<1, true>(in, o, lt);
+    same = same && eq(o[0], log_f32_via_tab(x, lt));
+  } else if (what == 3) {
+    const float nb = (float)kBins, rnb = 1.0f / (float)kBins;
+    const float want = div_by_uniform(x, nb, rnb);
+    const f32x2 a = div_by_uniform2(f32x2{x, 1.5f}, nb, rnb), b = div_by_uniform2(f32x2{3.f, x}, nb, rnb);
+    same = eq(a.x, want) && eq(b.y, want) && eq(a.y, div_by_uniform(1.5f, nb, rnb)) &&
+           eq(b.x, div_by_uniform(3.f, nb, rnb));
+  } else if (what == 4) {
+    if ((bits >> 31) == 0u || x != x) same = eq(fsqrt_wave(x), fsqrt(x));
+  } else if (what == 5) {
+    const float tn = 2.f * x, t1 = 1.f + tn;
+    same = eq(fdiv_1c(tn, t1 + 0.0001f), fdiv(tn, t1 + 0.0001f));
+  } else {
+    if (x >= 0x1p-100f && x < __builtin_inff()) {
+      const float r = __builtin_amdgcn_rsqf(x);
+      float g = x * r;
+      const float h = 0.5f * r;
+      const float e = __builtin_fmaf(-h, g, 0.5f);
+      g = __builtin_fmaf(g, e, g);
+      const float d = __builtin_fmaf(-g, g, x);
+      same = eq(__builtin_fmaf(d, h, g), fsqrt(x));
+    }
+  }
+  if (!same) {
+    const unsigned k = atomicAdd(n_bad, 1u);
+    if (k < 64) bad_bits[k] = bits;
+  }
+}
+
 }  // namespace
 
 namespace aspns {
+
+hipError_t launch_debug_shortdiv_wave(int what, unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits,
+                                      const NsTables* T, hipStream_t s) {
+  if (what < 0 || what > 6) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(debug_shortdiv_wave_kernel, dim3((count + 255u) / 256u), dim3(256), 0, s, what, start, count,
+                     n_bad, bad_bits, T);
+  return hipGetLastError();
+}
 
 hipError_t launch_debug_fallbacks_wave(int what, unsigned start, unsigned count, unsigned* n_bad, unsigned* bad_bits,
                                        const NsTables* T, hipStream_t s) {

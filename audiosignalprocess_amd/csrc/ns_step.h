@@ -36,6 +36,11 @@ __device__ __forceinline__ float ns_div_bins(float a) {
   return div_by_uniform(a, (float)NB, 1.0f / (float)NB);
 }
 #define DIV129(a) ns_div_bins<kBins>(a)
+template <int NB>
+__device__ __forceinline__ f32x2 ns_div_bins2(f32x2 a) {  // two at a time (ns_kernels1.hip)
+  return div_by_uniform2(a, (float)NB, 1.0f / (float)NB);
+}
+#define DIV129_2(a) ns_div_bins2<kBins>(a)
 
 // One step of a quantile tracker (ns_core.c:232-260) in the branch-free form of the frame kernels: delta = FACTOR /
 // max(density, 1) (the quotient by 1 is exact), the step carries its sign -- lq += (+QUANTILE delta) / n or (-(1 -
@@ -61,6 +66,28 @@ __device__ __forceinline__ void tracker_step2(f32x2& lq, f32x2& den, f32x2 lm, f
 __device__ __forceinline__ void tracker_step1(float& lq, float& den, float lm, float cnt, float cnt1, float rcnt1) {
   const float fac = NS_FACTOR * 1.f, qp = NS_QUANTILE, qm = -(1.f - NS_QUANTILE), wd = NS_WIDTH;
   const float delta = fdiv(fac, fmax_raw(den, 1.0f));
+  const float coef = lm > lq ? qp : qm;
+  lq = lq + div_by_uniform(coef * delta, cnt1, rcnt1);
+  const float nd = div_by_uniform(cnt * den + 1.f / (2.f * wd), cnt1, rcnt1);
+  den = fabsf(lm - lq) < wd ? nd : den;
+}
+// The same two steps with the step quotient in its short form (ns_kernels1.hip; the forms above keep their text).  The
+// numerator is the constant FACTOR and the divisor is at least 1, so delta is a function of one float: fdiv_c equals
+// fdiv there on every bit pattern max(density, 1) can be (ns_device.h; swept on the device, NaN and +inf included).
+__device__ __forceinline__ float fdiv40(float dm) { return fdiv_c(NS_FACTOR * 1.f, dm); }      // dm == max(den, 1)
+__device__ __forceinline__ f32x2 fdiv40_2(f32x2 dm) { return fdiv2_c(NS_FACTOR * 1.f, dm); }
+__device__ __forceinline__ void tracker_step2_c(f32x2& lq, f32x2& den, f32x2 lm, float cnt, float cnt1, float rcnt1) {
+  const f32x2 dm = {fmax_raw(den.x, 1.0f), fmax_raw(den.y, 1.0f)};
+  const float qp = NS_QUANTILE, qm = -(1.f - NS_QUANTILE), wd = NS_WIDTH;
+  const f32x2 delta = fdiv40_2(dm);
+  const f32x2 coef = {lm.x > lq.x ? qp : qm, lm.y > lq.y ? qp : qm};
+  lq = lq + div_by_uniform2(coef * delta, cnt1, rcnt1);
+  const f32x2 nd = div_by_uniform2(f32x2{cnt, cnt} * den + f32x2{1.f / (2.f * wd), 1.f / (2.f * wd)}, cnt1, rcnt1);
+  den = f32x2{fabsf(lm.x - lq.x) < wd ? nd.x : den.x, fabsf(lm.y - lq.y) < wd ? nd.y : den.y};
+}
+__device__ __forceinline__ void tracker_step1_c(float& lq, float& den, float lm, float cnt, float cnt1, float rcnt1) {
+  const float qp = NS_QUANTILE, qm = -(1.f - NS_QUANTILE), wd = NS_WIDTH;
+  const float delta = fdiv40(fmax_raw(den, 1.0f));
   const float coef = lm > lq ? qp : qm;
   lq = lq + div_by_uniform(coef * delta, cnt1, rcnt1);
   const float nd = div_by_uniform(cnt * den + 1.f / (2.f * wd), cnt1, rcnt1);

@@ -984,7 +984,7 @@ NSX_HD inline void process_core(AspNsxState& s, NsxWork& w, int16_t* hist, const
       w.postSnr[i] = post;
       const uint32_t nearMagnEst = (uint32_t)s.prevMagnU16[i] * (uint32_t)s.noiseSupFilter[i];
       u1 = nearMagnEst << 3;
-      const uint32_t p = nShifts >= 0 ? s.prevNoiseU32[i] >> nShifts : s.prevNoiseU32[i] << -nShifts;
+      const uint32_t p = s.prevNoiseU32[i] >> (nShifts & 31);   // a negative count as the reference build takes it: modulo 32
       if (p > 0) {
         u1 /= p;
         u1 = satMax < u1 ? satMax : u1;

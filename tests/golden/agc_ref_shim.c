@@ -17,6 +17,15 @@ void* agc_ref_create(void) {
 
 size_t agc_ref_sizeof(void) { return sizeof(LegacyAgc); }
 
+/* the seeded cases of tests/agc_runs.py: one scalar field of the instance by name; -1 for a name not listed */
+int agc_ref_set(void* h, const char* name, int value) {
+  LegacyAgc* a = (LegacyAgc*)h;
+#define SET(f) if (strcmp(name, #f) == 0) { a->f = value; return 0; }
+  SET(msZero) SET(zeroCtrlMax)
+#undef SET
+  return -1;
+}
+
 #define COPY(f) o->f = a->f
 #define COPY_ARR(f) memcpy(o->f, a->f, sizeof o->f)
 #define COPY_VAD(dst, src)                                        \

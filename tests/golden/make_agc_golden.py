@@ -1,4 +1,14 @@
-"""Writes tests/golden/agc_golden.npz from the reference gain control compiled in place:
+"""Writes tests/golden/agc_golden.npz and tests/golden/agc_edges_golden.npz from the reference gain control compiled in
+place (oracle/Makefile: _ref/libagc_ref.so, which build() makes where the reference is present):
+
+    python tests/golden/make_agc_golden.py [--edges] [--check] [libagc_ref.so [libagc_ref_counting.so]]
+
+Without --edges: the golden runs (tests/agc_runs.RUNS) and the gain-table grid into agc_golden.npz.  With --edges:
+EDGE_RUNS, the SEEDED case and EDGE_GRID into agc_edges_golden.npz; a run longer than 120 frames keeps its output
+samples for the 20 frames from each snapshot on and a sha256 per block of 50 frames (tests/edge_pack.py).  --check
+writes nothing: it regenerates every array from the reference build and compares it with the committed file (the
+counting build below plays no part in that).  The first library's recipe, and the second's, which the writer follows
+itself in a temporary directory when no second library is named:
 
     R=<reference>/WebRtc_AMP_Port; A=$R/webrtc/common_audio/signal_processing
     M=$R/webrtc/modules/audio_processing/agc/legacy
@@ -50,7 +60,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 from audiosignalprocess_amd.agc import AspAgcState, WebRtcAgcConfig, state_dict  # noqa: E402
-from tests.agc_runs import RUNS, inputs, replay  # noqa: E402
+from tests import agc_runs  # noqa: E402
+from tests.edge_pack import pack_state  # noqa: E402
+from tests.agc_runs import EDGE_GRID, EDGE_RUNS, RUNS, SEEDED, inputs, replay  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(HERE))
+DEFAULT_LIB = os.path.join(ROOT, "oracle", "_ref", "libagc_ref.so")
 
 GRID = [(c, t, l, a) for c in (0, 3, 9, 15, 20, 30, 45, 90) for t in (0, 3, 6, 12, 31) for l in (0, 1)
         for a in (4, 8, 12, 20, 30)]
@@ -140,7 +155,9 @@ class Ref:
         return rc, y, out.value, sat.value
 
     def snapshot(self, f):
-        if f in self.spec["snaps"]:
+        if f in self.spec["snaps"] and self.key.startswith("e"):   # an edge run: the state as one array
+            self.data["%s_s%d" % (self.key, f)] = pack_state(AspAgcState, state_dict(self.state()))
+        elif f in self.spec["snaps"]:
             for n, v in state_dict(self.state()).items():
                 self.data["%s_s%d_%s" % (self.key, f, n)] = v
 
@@ -148,19 +165,50 @@ class Ref:
         self.L.WebRtcAgc_Free(self.h)
 
 
-def main():
-    L = load(sys.argv[1])
+def input_sha(spec):
+    sha = hashlib.sha256()
+    for x, far in inputs(spec):
+        sha.update(x.tobytes())
+        if far is not None:
+            sha.update(far.tobytes())
+    return np.frombuffer(sha.digest(), np.uint8)
+
+
+def build_counting(tmp):
+    """The docstring's second recipe: the same build with four counters in a scratch copy of digital_agc.c, in tmp."""
+    import re
+    import subprocess
+
+    R = os.path.join(os.environ.get("REF", "/root/reference"), "WebRtc_AMP_Port")
+    A = os.path.join(R, "webrtc", "common_audio", "signal_processing")
+    M = os.path.join(R, "webrtc", "modules", "audio_processing", "agc", "legacy")
+    with open(os.path.join(M, "digital_agc.c")) as f:
+        src = f.read()
+    for pat, rep in ((r"^static const int16_t kAvgDecayTime", "int agc_limiter_hits, agc_limiter_wide_hits, agc_gate_wide_hits, agc_first_clip_hits;\n\\g<0>"),
+                     (r"// multiply by 253/256 ==> -0.1 dB", "agc_limiter_hits++;"),
+                     (r"gains\[k \+ 1\] = \(gains\[k\+1\] / 256\) \* 253;", "\\g<0> agc_limiter_wide_hits++;"),
+                     (r"tmp32 \*= 178 \+ gain_adj;", "\\g<0> agc_gate_wide_hits++;"),
+                     (r"out\[i\]\[n\] = \(int16_t\)32767;", "\\g<0> agc_first_clip_hits++;"),
+                     (r"out\[i\]\[n\] = \(int16_t\)-32768;", "\\g<0> agc_first_clip_hits++;")):
+        src, k = re.subn(pat, rep, src, flags=re.M)
+        assert k >= 1, pat
+    with open(os.path.join(tmp, "digital_agc_count.c"), "w") as f:
+        f.write(src)
+    lib = os.path.join(tmp, "libagc_ref_counting.so")
+    subprocess.run(["gcc", "-O2", "-fwrapv", "-fPIC", "-shared", "-w", "-I" + R, "-I" + M, "-I" + os.path.join(ROOT, "include"),
+                    os.path.join(M, "analog_agc.c"), os.path.join(tmp, "digital_agc_count.c")] +
+                   [os.path.join(A, f) for f in ("resample_by_2.c", "dot_product_with_scale.c", "division_operations.c", "spl_sqrt.c",
+                                                 "copy_set_operations.c")] + [os.path.join(HERE, "agc_ref_shim.c"), "-o", lib], check=True)
+    return lib
+
+
+def golden_arrays(L, counting, check):
     data, seen = {}, {}
     for i, spec in enumerate(RUNS):
-        sha = hashlib.sha256()
-        for x, far in inputs(spec):
-            sha.update(x.tobytes())
-            if far is not None:
-                sha.update(far.tobytes())
         r = Ref(L, spec, data, "r%d" % i)
         out, levels, sats, rcs = replay(spec, r)
         r.close()
-        data["r%d_sha" % i] = np.frombuffer(sha.digest(), np.uint8)
+        data["r%d_sha" % i] = input_sha(spec)
         data["r%d_out" % i], data["r%d_level" % i], data["r%d_sat" % i], data["r%d_rc" % i] = out, levels, sats, rcs
         for k in r.seen:
             seen.setdefault(k, []).append(i)
@@ -172,7 +220,21 @@ def main():
         print("%-18s runs %s" % (k, seen.get(k)))
     missing = [k for k in want if k not in seen]
     assert not missing, "the runs do not reach: %r" % missing
-    K = load(sys.argv[2])
+    table = np.zeros((len(GRID), 33), np.int32)
+    for k, (c, t, l, a) in enumerate(GRID):
+        table[k, 0] = L.WebRtcAgc_CalculateGainTable(table[k, 1:].ctypes.data, c, t, l, a)
+    data["gain_grid"] = np.array(GRID, np.int32)
+    data["gain_tables"] = table
+    if check:
+        return data
+    import tempfile
+
+    with tempfile.TemporaryDirectory() as tmp:
+        counted(load(counting or build_counting(tmp)), data)
+    return data
+
+
+def counted(K, data):
     names = ["agc_limiter_hits", "agc_limiter_wide_hits", "agc_gate_wide_hits", "agc_first_clip_hits"]
     hits = {name: [] for name in names}
     for i, spec in enumerate(RUNS):
@@ -188,13 +250,58 @@ def main():
     for name in names:
         print("%-22s runs %s" % (name, hits[name]))
     assert all(hits[name] for name in names), hits
-    table = np.zeros((len(GRID), 33), np.int32)
-    for k, (c, t, l, a) in enumerate(GRID):
+
+
+def edge_arrays(L):
+    data = {}
+    for i, spec in enumerate(EDGE_RUNS):
+        r = Ref(L, spec, data, "e%d" % i)
+        out, levels, sats, rcs = replay(spec, r)
+        r.close()
+        data["e%d_sha" % i] = input_sha(spec)
+        data["e%d_keep" % i], data["e%d_blocks" % i] = agc_runs.pack_outputs(spec, out)
+        data["e%d_level" % i], data["e%d_sat" % i], data["e%d_rc" % i] = levels, sats, rcs
+        d = np.diff(levels)
+        print("edge run", i, "done: levels", levels.min(), "..", levels.max(), "steps up", int((d > 0).sum()), "down", int((d < 0).sum()),
+              "rc", sorted(set(rcs.tolist())), sorted(r.seen))
+    for k, case in enumerate(SEEDED):
+        spec = dict(EDGE_RUNS[case["base"]], snaps=())
+        r = Ref(L, spec, {}, "x")
+        level = int(replay(spec, r, stop=case["at"])[1][-1])
+        L.agc_ref_set.argtypes = [P, C.c_char_p, C.c_int]
+        for name, v in case["plant"].items():
+            assert L.agc_ref_set(r.h, name.encode(), v) == 0, name
+        data["sd%d_in" % k] = pack_state(AspAgcState, state_dict(r.state()))
+        data["sd%d_level_in" % k] = np.array([level], np.int32)
+        out, levels, sats, rcs = agc_runs.replay_seeded(case, r, level)
+        data["sd%d_out" % k], data["sd%d_level" % k], data["sd%d_sat" % k], data["sd%d_rc" % k] = out, levels, sats, rcs
+        data["sd%d_s" % k] = pack_state(AspAgcState, state_dict(r.state()))
+        r.close()
+        print("seeded case", k, "done: levels", levels.tolist())
+    table = np.zeros((len(EDGE_GRID), 33), np.int32)
+    for k, (c, t, l, a) in enumerate(EDGE_GRID):
         table[k, 0] = L.WebRtcAgc_CalculateGainTable(table[k, 1:].ctypes.data, c, t, l, a)
-    data["gain_grid"] = np.array(GRID, np.int32)
+    data["gain_grid"] = np.array(EDGE_GRID, np.int32)
     data["gain_tables"] = table
-    np.savez_compressed(os.path.join(HERE, "agc_golden.npz"), **data)
-    print(os.path.getsize(os.path.join(HERE, "agc_golden.npz")), "bytes")
+    return data
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    edges, check = "--edges" in sys.argv, "--check" in sys.argv
+    L = load(args[0] if args else DEFAULT_LIB)
+    data = edge_arrays(L) if edges else golden_arrays(L, args[1] if len(args) > 1 else None, check)
+    path = os.path.join(HERE, "agc_edges_golden.npz" if edges else "agc_golden.npz")
+    if check:
+        have = np.load(path)
+        bad = sorted(set(have.files) ^ set(data)) + [k for k in data if k in have.files and not (
+            have[k].dtype == data[k].dtype and np.array_equal(have[k], data[k]))]
+        print("%s: %d arrays regenerated, %d differ" % (os.path.basename(path), len(data), len(bad)))
+        if bad:
+            raise SystemExit("differing arrays: %r" % bad[:12])
+        return
+    np.savez_compressed(path, **data)
+    print(os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":

@@ -2,7 +2,8 @@
 frames.  Shared by the golden writer and the tests, so both replay the same call sequence."""
 import numpy as np
 
-from audiosignalprocess_amd.synth import nsx_frames
+from audiosignalprocess_amd.synth import agc_frames, nsx_frames
+from tests.edge_pack import BLOCK, KEEP, compare_outputs, kept_frames, pack_outputs  # noqa: F401
 
 BANDS = {8000: 1, 16000: 1, 32000: 2, 48000: 3}
 
@@ -16,6 +17,79 @@ RUNS = [
     dict(fs=16000, mode=0, frames=80, seed=6, snaps=(3, 70, 79), events="quiet"),
     dict(fs=16000, mode=1, frames=232, seed=7, snaps=(45, 120, 150, 199, 231), events="mid"),
 ]
+
+# The edge runs (tests/golden/nsx_edges_golden.npz): the same schedule and snapshot conventions; each is there for lines
+# of csrc/nsx_core.h that no run above reaches (tools/core_branch_report.py nsx both).  src="agc": the input is the gain
+# control's programme (synth.agc_frames), whose all-zero stretches do not count towards the 512-frame histogram window;
+# "shape": frames [a, b) reshaped by shaped() below.  Snapshots sit on the frame of the event a run is there for and on
+# the frame after it.
+_TAPS = ((0, 121, -32768), (1, 25, 8000), (1, 89, 32767), (1, 153, -11500))
+EDGE_RUNS = [
+    # talk with silences, policy 2; the window closes at frame 630: the flatness histogram's weight test fails
+    # (useFlat = 0, 675), the first merge test's arms (670), the u3 normalisation loop (1012-1014)
+    dict(fs=16000, mode=2, frames=660, seed=3, level=9000, src="agc", snaps=(40, 630, 631, 659)),
+    # the same at 8 kHz (128-point transforms): 675 and the t < minLrt clamp (663)
+    dict(fs=8000, mode=2, frames=660, seed=3, level=3000, src="agc", snaps=(40, 630, 631, 659)),
+    # noise near full scale: the LRT histogram does not fluctuate, thresholdLogLrt = maxLrt (659-660), useDiff = 0 (665), 1013;
+    # the close leaves the flatness feature in use, and 25 frames of an exact DC (empty bins: the feature decays by 0.3
+    # a frame) take it under its threshold: the indicator's other side (755)
+    dict(fs=16000, mode=1, frames=540, seed=1, level=30000, shape=[(515, 540, "dc", 20000, 0)], snaps=(30, 511, 512, 530, 539)),
+    # 210 faint frames, then the same noise a hundred times louder: the close at 511 finds curAvgMagnEnergy far above
+    # timeAvgMagnEnergy and clamps featureSpecDiff to 0x007FFFFF (1023-1024); the difference histogram's index leaves it (635)
+    dict(fs=16000, mode=1, frames=540, seed=31, level=30000, shape=[(0, 210, "gain", 1, 100)], snaps=(100, 211, 511, 512, 539)),
+    # the same with a start a thousand times fainter: timeAvgMagnEnergy stays 0 (634, 1009), w1 < 154 on the difference
+    # histogram (688), intPart < -8 (797)
+    dict(fs=16000, mode=1, frames=540, seed=31, level=30000, shape=[(0, 210, "gain", 1, 1000)], snaps=(100, 211, 511, 512, 539)),
+    # 300 frames of a full-scale square wave, which the noise estimate settles on, then |x| <= 1: prevQNoise + 11 < qMagn,
+    # the nShifts < 0 arm of the gain (1096-1098: the branch only, see core_branch_exemptions.BRANCH_ONLY), and the prior
+    # SNR's shift by a negative count (987), whose value the outputs do depend on
+    dict(fs=8000, mode=2, frames=340, seed=12, level=20, shape=[(0, 300, "square", 16, 32767), (300, 340, "dc", 0, 1)],
+         snaps=(50, 299, 300, 301, 339)),
+    # one smooth hump that fills the analysis buffer of frame 5, zeros around it: from bin 5 up the spectrum is empty,
+    # sum_log_magn < 2^14 and the pink-noise fit's zeros clamp and tmp_u16 arm run (366, 372-373)
+    dict(fs=8000, mode=2, frames=12, seed=32, level=20, shape=[(0, 12, "bump", 352, 128, 32767)], snaps=(4, 5, 11)),
+    dict(fs=16000, mode=2, frames=12, seed=32, level=20, shape=[(0, 12, "bump", 704, 256, 32767)], snaps=(4, 5, 11)),
+    # every other sample +-2 from frame 0: a faint spectrum that rises with frequency, the fit's numerator is
+    # negative and clamps to 0 (380); initMagnEst of an empty bin is 0 (933)
+    dict(fs=16000, mode=2, frames=12, seed=32, level=20, shape=[(0, 12, "comb", 2, 2)], snaps=(0, 1, 11)),
+    # 60 frames of |x| <= 2, then frames of four single samples a quarter of the buffer apart, placed so that the
+    # inverse transform's first seven stages stay at or under 13573 and its last one meets 27600: the second scaling
+    # step of the inverse FFT (217-220), a wave maximum that moves shift, scale and round2 of every lane
+    dict(fs=16000, mode=0, frames=72, seed=41, level=20, shape=[(0, 60, "dc", 0, 2), (60, 72, "taps", 2, _TAPS)],
+         snaps=(59, 61, 62, 71)),
+]
+
+# Seeded cases: the histograms of RUNS[base] after frame `at` are replaced, then `frames` more frames of that run follow
+# (the window closes on the second of them).  The reference can hold each of these states: a histogram entry counts
+# the frames of the window whose feature fell into that bin (nsx_core.c, FeatureParameterExtraction, flag 0: one
+# increment per histogram and frame, none when the index is outside), so any non-negative entries whose sum is at most
+# cntThresUpdate are the trace of some 510 frames; cntThresUpdate and blockIndex are left as the run left them.
+SEEDED = [
+    # both two-peak merges, made to matter: the flatness peaks 120 at position 33 and 100 at 31 merge to 220 at 32, so
+    # useFlat = 1 only with the merged weight and thresholdSpecFlat = 922 x 32 inside its clamps (670-672); the difference
+    # peaks 90 at 11 and 80 at 9 merge to 170 at 10: useDiff = 1 only merged, thresholdSpecDiff = 60 (682-684)
+    dict(base=1, at=509, frames=3, plant=dict(histLrt={2: 200, 60: 200}, histSpecFlat={15: 100, 16: 120}, histSpecDiff={4: 80, 5: 90})),
+    # no LRT count under bin 10: num == 0 (659); a flatness peak that weighs 100 < 154 (674, first term)
+    dict(base=1, at=509, frames=3, plant=dict(histLrt={30: 300}, histSpecFlat={40: 100}, histSpecDiff={10: 200})),
+    # 6 avgHist > 100 num (659, third term); a flatness peak at position 81: 922 p1 clamps to 38912 (678); a difference
+    # peak in bin 0: 6 p1 < 16 clamps to 16 (687)
+    dict(base=1, at=509, frames=3, plant=dict(histLrt={9: 300, 100: 100}, histSpecFlat={40: 300}, histSpecDiff={0: 200})),
+    # the LRT threshold near its upper end (6 avgHist = 66 num), a flatness peak at position 11 < 24 with weight enough (674)
+    dict(base=1, at=509, frames=3, plant=dict(histLrt={5: 200, 60: 200}, histSpecFlat={5: 200}, histSpecDiff={10: 200})),
+]
+HIST_FIELDS = ("histLrt", "histSpecFlat", "histSpecDiff")
+
+
+def plant(st, case):
+    """Writes the case's histograms into a state struct (the reference's or AspNsxState): all zero but the named bins."""
+    for name in HIST_FIELDS:
+        h = getattr(st, name)
+        for i in range(len(h)):
+            h[i] = case["plant"][name].get(i, 0)
+
+
+def seeded_inputs(case):
+    return inputs(RUNS[case["base"]])[case["at"] + 1:case["at"] + 1 + case["frames"]]
 
 
 def schedule(spec):
@@ -50,6 +124,29 @@ def rates(spec):
     return out
 
 
+def shaped(x, t, kind, arg):
+    """One frame of a "shape" stretch: x int64 [bands][n] from the synth, t the sample index in the run."""
+    if kind == "gain":       # x * num // den
+        y = x * arg[0] // arg[1]
+    elif kind == "dc":       # a constant plus the synth's noise folded into [-dither, dither]
+        y = arg[0] + (x % (2 * arg[1] + 1) - arg[1])
+    elif kind == "square":   # a square wave of the given period and amplitude, on every band
+        y = np.where((t // (arg[0] // 2)) % 2 == 0, arg[1], -arg[1])[None, :] + 0 * x
+    elif kind == "comb":     # one sample in `period` at the amplitude, alternating in sign, the rest zero
+        y = np.where(t % arg[0] == arg[2] if len(arg) > 2 else t % arg[0] == 0, np.where((t // arg[0]) % 2 == 0, arg[1], -arg[1]), 0)[None, :] + 0 * x
+    elif kind == "taps":     # single samples: (frame phase, position in the frame, value) with the frame counted modulo arg[0]
+        y = 0 * x
+        for phase, pos, val in arg[1]:
+            if (t[0] // t.size) % arg[0] == phase:
+                y[:, pos] = val
+    elif kind == "bump":     # amp * 16 u^2 (L - u)^2 / L^4 for u = t - start in [0, L), zero elsewhere: one smooth hump
+        u = np.clip(t - arg[0], 0, arg[1])
+        y = (arg[2] * 16 * u * u * (arg[1] - u) * (arg[1] - u) // arg[1] ** 4)[None, :] + 0 * x
+    else:
+        raise ValueError(kind)
+    return np.clip(y, -32768, 32767).astype(np.int16)
+
+
 def inputs(spec):
     """One list entry per frame: int16 [bands][n] of stream 0 of synth.nsx_frames at the frame's rate."""
     F = spec["frames"]
@@ -57,7 +154,10 @@ def inputs(spec):
     gen = {}
     for fs in set(rs):
         n = 80 if fs == 8000 else 160
-        gen[fs] = nsx_frames(1, F, n, BANDS[fs], seed=spec["seed"], level=spec.get("level", 800))[:, :, 0]
+        if spec.get("src") == "agc":   # the gain control's programme: talk, a noise floor, faint talk, silence, clipping talk
+            gen[fs] = agc_frames(1, F, n, BANDS[fs], seed=spec["seed"], level=spec["level"], shift=spec.get("shift", 0))[:, :, 0]
+        else:
+            gen[fs] = nsx_frames(1, F, n, BANDS[fs], seed=spec["seed"], level=spec.get("level", 800))[:, :, 0]
     e = spec.get("events")
     out = []
     for f in range(F):
@@ -70,5 +170,8 @@ def inputs(spec):
             x[:] = np.where((t // 37) % 2 == 0, 32767, -32768).astype(np.int16)
         if e == "quiet":
             x = (x.astype(np.int32) % 7 - 3).astype(np.int16)
+        for a, b, kind, *arg in spec.get("shape", ()):   # frames [a, b) of an edge run, reshaped in integer arithmetic
+            if a <= f < b:
+                x = shaped(x.astype(np.int64), f * n + np.arange(n), kind, arg)
         out.append(np.ascontiguousarray(x))
     return out

@@ -44,6 +44,7 @@ def _lib():
             "AspAecBatch_ProcessV": [vp, vp, vp, ip, vp, vp, vp, ip],
             "AspAecBatch_InitStream": [vp, ip],
             "AspAecBatch_GetControlStream": [vp, ip, C.POINTER(AspAecControl)],
+            "AspAecBatch_RunList": [vp, vp, vp, ip, vp, vp, vp, ip, ip, vp, vp, ip],
             "AspAecBatch_TimedSteps": [vp, vp, vp, vp, ip, ip, ip, C.POINTER(C.c_float)],
             "AspAec_rdft128_batch": [vp, vp, ip, ip, ip],
             "AspAec_host_table": [ip, vp, ip],
@@ -170,6 +171,45 @@ class AecBatch:
                                       n, num_frames, delay_ms, MEM_DEVICE)
         if rc not in (0, -1):
             raise AspError("AspAecBatch_Run failed (%d)" % rc)
+
+    def run_list(self, streams, counts, far, near, delays_ms, max_frames=None, out=None):
+        """BufferFarend + Process of the listed streams, entry i by counts[i] frames with the reported delay
+        delays_ms[i] (AspAecBatch_RunList).  far / near [max_frames][len(streams)][n] -> (out, status [len(streams)]);
+        rows f >= counts[i] of out are not written (out: the float32 array to write into, `near` itself for in place;
+        default a new one)."""
+        streams = np.ascontiguousarray(streams, np.int32)
+        counts = np.ascontiguousarray(counts, np.int32)
+        ms = np.ascontiguousarray(delays_ms, np.int16)
+        far = np.ascontiguousarray(far, np.float32)
+        near = np.ascontiguousarray(near, np.float32)
+        if max_frames is None:
+            max_frames = far.shape[0]
+        assert streams.shape == counts.shape == ms.shape and streams.ndim == 1
+        assert far.shape == near.shape and far.shape[:2] == (max_frames, len(streams))
+        if out is None:
+            out = np.empty_like(near)
+        assert out.dtype == np.float32 and out.shape == near.shape and out.flags.c_contiguous
+        status = np.zeros(len(streams), np.int32)
+        rc = self.lib.AspAecBatch_RunList(self.h, streams.ctypes.data, counts.ctypes.data, len(streams), far.ctypes.data,
+                                          near.ctypes.data, out.ctypes.data, far.shape[2], max_frames, ms.ctypes.data,
+                                          status.ctypes.data, MEM_HOST)
+        if rc not in (0, -1):
+            raise AspError("AspAecBatch_RunList failed (%d)" % rc)
+        return out, status
+
+    def run_list_device(self, streams, counts, far_ptr, near_ptr, out_ptr, n, max_frames, delays_ms):
+        """run_list on device buffers [max_frames][len(streams)][n], enqueued on the batch's stream -> status."""
+        streams = np.ascontiguousarray(streams, np.int32)
+        counts = np.ascontiguousarray(counts, np.int32)
+        ms = np.ascontiguousarray(delays_ms, np.int16)
+        assert streams.shape == counts.shape == ms.shape and streams.ndim == 1
+        status = np.zeros(len(streams), np.int32)
+        rc = self.lib.AspAecBatch_RunList(self.h, streams.ctypes.data, counts.ctypes.data, len(streams),
+                                          C.c_void_p(far_ptr), C.c_void_p(near_ptr), C.c_void_p(out_ptr), n, max_frames,
+                                          ms.ctypes.data, status.ctypes.data, MEM_DEVICE)
+        if rc not in (0, -1):
+            raise AspError("AspAecBatch_RunList failed (%d)" % rc)
+        return status
 
     def timed_steps(self, far_ptr, near_ptr, out_ptr, n, frames_in_ring, steps):
         ms = C.c_float()

@@ -48,6 +48,9 @@ hipError_t launch_aec_farend_v(float* state, float* far_ring, const AecTables* T
                                const FarOps* vfar, int nrOfSamples, int num_part, hipStream_t s);
 hipError_t launch_aec_process_v(float* state, float* far_ring, const AecTables* T, const float* nearend, float* out,
                                 int num_streams, int nrOfSamples, const AecStreamStep* vdesc, int num_part, hipStream_t s);
+hipError_t launch_aec_list(float* state, float* far_ring, const AecTables* T, const float* farend, const float* nearend,
+                           float* out, int num_streams, int nrOfSamples, int n, const AecListEntry* list,
+                           const AecListStep* descs, int stride, const ProcOps& batch_ops, int num_part, hipStream_t s);
 hipError_t launch_aec_delay(DelayBlock* blocks, const float* spectra, int num_streams, const DelayOps& ops,
                             hipStream_t s);
 hipError_t launch_aec_resample(float* rs_buffer, const float* farend, float* out, int num_streams, int size, int size_out,
@@ -194,6 +197,12 @@ struct AspAecBatch {
   FarOps* vfar_host = nullptr;               // [S], pinned: this call's far-end work of every stream
   FarOps* vfar_dev = nullptr;
   hipEvent_t vev = nullptr;                  // the last per-stream launch has read its descriptors
+  // List calls (AspAecBatch_RunList): a ring of kAecListSlots slots, each one launch's entries [S] and descriptors
+  // [S][kAecListMaxFrames]; allocated by the first list call
+  unsigned char* list_host = nullptr;        // pinned
+  unsigned char* list_dev = nullptr;
+  hipEvent_t list_ev[kAecListSlots] = {};    // slot i's launch has read its descriptors
+  int list_slot = 0;
   // echo metrics (aec_core.c:548-770): [S][kMetDwords], updated by the kernel when metricsMode is on
   float* metrics = nullptr;
 };
@@ -730,6 +739,30 @@ int frame_device(AspAecBatch* b, DeviceIssuer& iss, const float* far_dev, const 
   return process_device(b->su, b->ctl, iss, n, msInSndCardBuf, rc);
 }
 
+// ------------------------------------------------------------------ list calls (AspAecBatch_RunList)
+static_assert(kAecListMaxFrames == ASP_AEC_LIST_MAX_FRAMES && kAecListSlots == ASP_AEC_LIST_SLOTS && sizeof(AecListStep) == 176 &&
+                  sizeof(AecListEntry) == 8, "the figures include/asp_aec.h states");
+size_t list_slot_bytes(const AspAecBatch* b) {
+  return (size_t)b->S * (sizeof(AecListEntry) + (size_t)kAecListMaxFrames * sizeof(AecListStep));
+}
+int list_resources(AspAecBatch* b) {
+  if (b->list_dev) return 0;
+  AEC_TRY(hipHostMalloc((void**)&b->list_host, list_slot_bytes(b) * kAecListSlots, hipHostMallocDefault));
+  for (int i = 0; i < kAecListSlots; ++i) AEC_TRY(hipEventCreateWithFlags(&b->list_ev[i], hipEventDisableTiming));
+  AEC_TRY(hipMalloc((void**)&b->list_dev, list_slot_bytes(b) * kAecListSlots));
+  b->list_slot = 0;
+  return 0;
+}
+// the descriptors of one launch: [entry][frame] with `stride` frames per entry, or nowhere (a control-only handle)
+struct ListSlotSink final : AecListSink {
+  AecListStep* descs = nullptr;
+  int stride = 0;
+  int step(int entry, int frame, const AecListStep& d) override {
+    if (descs) descs[(size_t)entry * stride + frame] = d;
+    return 0;
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -818,6 +851,10 @@ int AspAecBatch_Free(AspAecBatch* b) {
   if (b->vfar_host) (void)hipHostFree(b->vfar_host);
   if (b->vfar_dev) (void)hipFree(b->vfar_dev);
   if (b->vev) (void)hipEventDestroy(b->vev);
+  if (b->list_host) (void)hipHostFree(b->list_host);
+  if (b->list_dev) (void)hipFree(b->list_dev);
+  for (int i = 0; i < kAecListSlots; ++i)
+    if (b->list_ev[i]) (void)hipEventDestroy(b->list_ev[i]);
   b->sync.release();
   if (b->flow_bits) (void)hipFree(b->flow_bits);
   if (b->flow_dev) (void)hipFree(b->flow_dev);
@@ -1015,6 +1052,139 @@ int AspAecBatch_GetControlStream(AspAecBatch* b, int stream, AspAecControl* c) {
   return ASP_OK;
 }
 
+// WebRtcAec_BufferFarend + WebRtcAec_Process of SOME streams, each by its own number of frames (include/asp_aec.h).
+// Everything is checked first; the control functions then run on copies of the listed streams' control planes, one
+// launch's frames at a time (aec_control.h, plan_list), and a launch's copies are committed once it is enqueued.
+int AspAecBatch_RunList(AspAecBatch* b, const int32_t* streams, const int32_t* counts, int n, const float* farend,
+                        const float* nearend, float* out, int nrOfSamples, int max_frames, const int16_t* msInSndCardBuf,
+                        int32_t* status, int mem) {
+  AspDeviceScope dev_scope_;
+  if (!b) return aec_fail(ASP_ERR_PARAM, "null batch handle");
+  if (!streams || !counts || !farend || !nearend || !out || !msInSndCardBuf)
+    return aec_fail(ASP_ERR_PARAM, "RunList: null pointer (only status may be null)");
+  if (mem != ASP_MEM_HOST && mem != ASP_MEM_DEVICE) return aec_fail(ASP_ERR_PARAM, "mem must be ASP_MEM_HOST or ASP_MEM_DEVICE");
+  if (nrOfSamples != 80 && nrOfSamples != 160) return aec_fail(ASP_ERR_PARAM, "RunList: nrOfSamples must be 80 or 160");
+  if (n < 0 || n > b->S) return aec_fail(ASP_ERR_PARAM, "RunList: n outside 0 .. num_streams");
+  if (max_frames < 0) return aec_fail(ASP_ERR_PARAM, "RunList: max_frames < 0");
+  int maxc = 0;
+  {
+    std::vector<char> seen((size_t)b->S, 0);
+    for (int i = 0; i < n; ++i) {
+      if (streams[i] < 0 || streams[i] >= b->S) return aec_fail(ASP_ERR_PARAM, "RunList: stream outside the batch");
+      if (seen[(size_t)streams[i]]) return aec_fail(ASP_ERR_PARAM, "RunList: stream listed twice");
+      seen[(size_t)streams[i]] = 1;
+      if (counts[i] < 0 || counts[i] > max_frames) return aec_fail(ASP_ERR_PARAM, "RunList: count outside 0 .. max_frames");
+      if (counts[i] > maxc) maxc = counts[i];
+    }
+  }
+  if (b->su.initFlag != kInitCheck) return aec_fail(ASP_ERR_STATE, "RunList: the batch is not initialised");
+  if (b->su.num_high > 0 || b->su.delay_logging || !b->su.reported_delay_enabled || b->su.skewMode == kAecTrue || b->su.metricsMode)
+    return aec_fail(ASP_ERR_STATE, "per-stream control covers the one-band configuration with reported delays "
+                                   "(no delay logging / delay-agnostic mode / skew compensation / metrics)");
+  if (n == 0 || max_frames == 0) return ASP_OK;  // nothing to do: the batch stays as it is, mode included
+  const bool dev = !control_only(b);
+  if (dev) AEC_TRY(dev_scope_.select(b->device));
+  if (const int rc = enter_vmode(b)) return rc;
+  if (maxc == 0) return ASP_OK;
+  if (dev) {
+    if (const int rc = list_resources(b)) return rc;
+  }
+  std::vector<AecCtl> work((size_t)n);
+  for (int i = 0; i < n; ++i) work[(size_t)i] = b->per[(size_t)streams[i]];
+  std::vector<int32_t> rcs((size_t)n, 0);
+  auto commit = [&] {
+    for (int i = 0; i < n; ++i) b->per[(size_t)streams[i]] = work[(size_t)i];
+  };
+  auto finish = [&] {
+    int any = 0;
+    for (int i = 0; i < n; ++i) {
+      if (status) status[i] = rcs[(size_t)i];
+      any |= rcs[(size_t)i];
+    }
+    return any;
+  };
+  ListSlotSink sink;
+  if (!dev) {
+    if (const int err = plan_list(b->su, work.data(), counts, n, 0, maxc, nrOfSamples, msInSndCardBuf, rcs.data(), sink)) return err;
+    commit();
+    return finish();
+  }
+  const size_t row = (size_t)n * nrOfSamples;  // one frame of all entries
+  const int chunk = maxc < kAecListMaxFrames ? maxc : kAecListMaxFrames;
+  const bool staged = mem == ASP_MEM_HOST;
+  float *dfar = nullptr, *dnear = nullptr, *dout = nullptr;
+  std::vector<float> back;
+  if (staged) {
+    hipError_t e = hipMalloc((void**)&dfar, row * chunk * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&dnear, row * chunk * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&dout, row * chunk * sizeof(float));
+    if (e != hipSuccess) {
+      if (dfar) (void)hipFree(dfar);
+      if (dnear) (void)hipFree(dnear);
+      return aec_fail(ASP_ERR_HIP, "RunList: staging", e);
+    }
+    back.resize(row * chunk);
+  }
+  int err = 0;
+  auto hip_step = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && err == 0) err = aec_fail(ASP_ERR_HIP, what, e);
+    return err == 0;
+  };
+  for (int f0 = 0; f0 < maxc && err == 0; f0 += kAecListMaxFrames) {
+    const int nf = maxc - f0 < kAecListMaxFrames ? maxc - f0 : kAecListMaxFrames;
+    const int slot = b->list_slot;
+    // the slot's previous launch must have read its descriptors before they are overwritten (a full ring: wait here)
+    if (!hip_step(hipEventSynchronize(b->list_ev[slot]), "RunList: descriptor slot")) break;
+    unsigned char* h = b->list_host + (size_t)slot * list_slot_bytes(b);
+    unsigned char* d = b->list_dev + (size_t)slot * list_slot_bytes(b);
+    AecListEntry* entries = reinterpret_cast<AecListEntry*>(h);
+    for (int i = 0; i < n; ++i) {
+      const int left = counts[i] - f0;
+      entries[i].stream = streams[i];
+      entries[i].count = left < 0 ? 0 : left < nf ? left : nf;
+    }
+    sink.descs = reinterpret_cast<AecListStep*>(h + (size_t)n * sizeof(AecListEntry));
+    sink.stride = nf;
+    err = plan_list(b->su, work.data(), counts, n, f0, nf, nrOfSamples, msInSndCardBuf, rcs.data(), sink);
+    if (err != 0) break;
+    const float *lf = farend + row * f0, *ln = nearend + row * f0;
+    float* lo = out + row * f0;
+    if (staged) {
+      if (!hip_step(hipMemcpyAsync(dfar, lf, row * nf * sizeof(float), hipMemcpyHostToDevice, b->stream), "RunList: upload")) break;
+      if (!hip_step(hipMemcpyAsync(dnear, ln, row * nf * sizeof(float), hipMemcpyHostToDevice, b->stream), "RunList: upload")) break;
+      lf = dfar;
+      ln = dnear;
+      lo = dout;
+    }
+    const size_t bytes = (size_t)n * sizeof(AecListEntry) + (size_t)n * nf * sizeof(AecListStep);
+    if (!hip_step(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, b->stream), "RunList: descriptors")) break;
+    if (!hip_step(launch_aec_list(b->state, b->far_ring, b->tables, lf, ln, lo, b->S, nrOfSamples, n,
+                                  reinterpret_cast<const AecListEntry*>(d),
+                                  reinterpret_cast<const AecListStep*>(d + (size_t)n * sizeof(AecListEntry)), nf,
+                                  batch_proc_ops(b->su), b->su.num_part, b->stream), "RunList: launch")) break;
+    commit();  // the device is now ahead by this launch's frames whatever follows
+    if (!hip_step(hipEventRecord(b->list_ev[slot], b->stream), "RunList: descriptor slot")) break;
+    b->list_slot = (slot + 1) % kAecListSlots;
+    if (staged) {
+      // only the rows the launch wrote go back: rows f >= counts[i] of `out` stay the caller's
+      if (!hip_step(hipMemcpyAsync(back.data(), dout, row * nf * sizeof(float), hipMemcpyDeviceToHost, b->stream), "RunList: download")) break;
+      if (!hip_step(hipStreamSynchronize(b->stream), "RunList: download")) break;
+      for (int i = 0; i < n; ++i)
+        for (int f = 0; f < entries[i].count; ++f)
+          memcpy(out + row * (f0 + f) + (size_t)i * nrOfSamples, back.data() + row * f + (size_t)i * nrOfSamples,
+                 (size_t)nrOfSamples * sizeof(float));
+    }
+  }
+  if (staged) {
+    (void)hipStreamSynchronize(b->stream);
+    (void)hipFree(dfar);
+    (void)hipFree(dnear);
+    (void)hipFree(dout);
+  }
+  if (err != 0) return err;
+  return finish();
+}
+
 static int process_impl(AspAecBatch* b, AspDeviceScope& dev_scope_, const float* nearend, const float* near_high, float* out,
                         float* out_high, int nrOfSamples, int msInSndCardBuf, int mem, int32_t skew) {
   if (b && out == nullptr) return set_error(b, AEC_NULL_POINTER_ERROR);
@@ -1180,6 +1350,8 @@ int AspAecBatch_Synchronize(AspAecBatch* b) {
   AEC_TRY(hipStreamSynchronize(b->stream));
   return aec_flow_check(b);
 }
+
+void* AspAecBatch_GetStream(AspAecBatch* b) { return b && !control_only(b) ? (void*)b->stream : nullptr; }
 
 int AspAecBatch_SetFlow(AspAecBatch* b, int mode) {
   AspDeviceScope dev_scope_;

@@ -405,19 +405,25 @@ inline void fill_agn_delay(AecSetup& su, DelayOps& d, int j, int nblocks, const 
   }
 }
 
-// WebRtcAec_ProcessFrames control plane (aec_core.c:1647-1778) -> one process descriptor.
-// `knownDelay`: the delay ProcessNormal / ProcessExtended hand over (echo_cancellation.c:735-741, 803-812)
-inline int process_frames_device(AecSetup& su, AecCtl& c, AecIssuer& iss, int n, int knownDelay) {
+// What every Process descriptor of a batch has alike: the fields that follow from the setup alone.
+inline ProcOps batch_proc_ops(const AecSetup& su) {
   ProcOps ops;
   memset(&ops, 0, sizeof ops);
-  const RingPos far_at_entry = c.far_pos;  // what the agnostic mode's first control step starts every stream from
-  const int system_delay_at_entry = c.system_delay;
-  const int kNumPart = su.num_part;
   ops.mult = su.mult;
   ops.nlp_mode = su.nlp_mode;
   ops.num_high = su.num_high;
   ops.mu = su.extended ? 0.4f : su.normal_mu;                                 // kExtendedMu, aec_core.c:172
   ops.error_threshold = su.extended ? 1.0e-6f : su.normal_error_threshold;    // kExtendedErrorThreshold, :173-175
+  return ops;
+}
+
+// WebRtcAec_ProcessFrames control plane (aec_core.c:1647-1778) -> one process descriptor.
+// `knownDelay`: the delay ProcessNormal / ProcessExtended hand over (echo_cancellation.c:735-741, 803-812)
+inline int process_frames_device(AecSetup& su, AecCtl& c, AecIssuer& iss, int n, int knownDelay) {
+  ProcOps ops = batch_proc_ops(su);
+  const RingPos far_at_entry = c.far_pos;  // what the agnostic mode's first control step starts every stream from
+  const int system_delay_at_entry = c.system_delay;
+  const int kNumPart = su.num_part;
   for (int j = 0; j < n; j += kFrameLen) {
     SubFrame& sf = ops.sub[ops.nsub++];
     rp_write(&c.near_pos, kFrameLen, &sf.near_wpos);
@@ -654,6 +660,68 @@ inline int process_device(AecSetup& su, AecCtl& c, AecIssuer& iss, int n, int ms
   }
   if (su.extended) return process_extended_device(su, c, iss, n, (int16_t)msInSndCardBuf);  // :377-394
   return process_normal_device(su, c, iss, n, (int16_t)msInSndCardBuf, skew, rc);
+}
+
+// ------------------------------------------------------------ list calls (AspAecBatch_RunList)
+// Where the descriptors of a list call go: `d` is frame `frame` (counted from the launch's first) of entry `entry`.
+struct AecListSink {
+  virtual int step(int entry, int frame, const AecListStep& d) = 0;
+
+ protected:
+  ~AecListSink() = default;
+};
+
+// The issuer of the planning step: what one BufferFarend + Process pair of one stream issues, as one descriptor.
+struct AecListRecorder final : AecIssuer {
+  AecListStep d;
+  int far_recorded = 0;
+  void begin() {
+    memset(&d, 0, sizeof d);
+    far_recorded = 0;
+  }
+  int farend(const float*, const FarOps& ops) override {
+    if (far_recorded++ != 0) return aec_refuse("list call: a far-end call of more than three partitions");
+    d.far = ops;
+    return 0;
+  }
+  int process(int, const ProcOps& ops, const float* far_src, const FarOps&, const AgnOps* agn, int) override {
+    if (far_src != nullptr || agn != nullptr || ops.agnostic || ops.spectra || ops.num_high)
+      return aec_refuse("list call: a Process descriptor outside per-stream control");
+    d.mode = 1;
+    d.ops = ops;
+    return 0;
+  }
+  int pass_through(int) override {
+    d.mode = 0;
+    return 0;
+  }
+  int delay(const DelayOps&) override { return aec_refuse("per-stream control runs no delay estimator"); }
+  int resample(const float**, int, int, float, float) override {
+    return aec_refuse("skew compensation runs on plain launches only");
+  }
+};
+
+// The planning step of a list call.  ctl[i] is the control plane of entry i's stream -- the caller hands in copies
+// and commits them once the launch is enqueued, so a refusal leaves the batch as it was.  Walks the entries and, of
+// each, frames frame0 .. min(counts[i], frame0 + frames) - 1 in order: WebRtcAec_BufferFarend, then WebRtcAec_Process
+// with the entry's reported delay ms[i], recorded as one descriptor and handed to `sink`; status[i] (may be null)
+// collects the OR of the reference's return values.
+inline int plan_list(AecSetup& su, AecCtl* ctl, const int32_t* counts, int n, int frame0, int frames, int nrOfSamples,
+                     const int16_t* ms, int32_t* status, AecListSink& sink) {
+  static const float kNoSamples = 0.f;  // the control functions take the far frame's address and never read it
+  AecListRecorder rec;
+  for (int i = 0; i < n; ++i) {
+    const int end = counts[i] < frame0 + frames ? counts[i] : frame0 + frames;
+    for (int f = frame0; f < end; ++f) {
+      rec.begin();
+      if (const int err = buffer_farend_device(su, ctl[i], rec, &kNoSamples, nrOfSamples)) return err;
+      int rc = 0;
+      if (const int err = process_device(su, ctl[i], rec, nrOfSamples, ms[i], &rc)) return err;
+      if (status) status[i] |= rc;
+      if (const int err = sink.step(i, f - frame0, rec.d)) return err;
+    }
+  }
+  return 0;
 }
 
 }  // namespace aspaec

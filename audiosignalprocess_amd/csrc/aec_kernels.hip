@@ -1861,6 +1861,97 @@ __global__ __launch_bounds__(256, NP == kNumPartNormal ? AEC_WAVES : 3) void aec
                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
+// ---- list calls (AspAecBatch_RunList): one wave per list entry; the wave walks its entry's frames in order, each the
+// far-end work and then the Process call of the per-stream kernels above (the same process_call<false, NP, false> body).
+// farend / nearend / out: [frames][n][nrOfSamples], frame f of entry i at (f * n + i) * nrOfSamples; descs:
+// [n][stride].  The state block and the far ring pass from one frame to the next through memory, as they do between
+// two launches; a wave's frames are ordered by program order, the lanes of the wave by the fence triple after each
+// frame (the one process_call puts after every block).  No counter is polled or published.
+// The launch's arguments sit in the kernel-argument segment and every frame reads the ones it needs from there again
+// (scalar loads): nothing but the frame counter is carried across a frame's work, which keeps the register budget that
+// of the per-stream kernel.
+struct AecListArgs {
+  float* state;
+  float* far_ring;
+  const AecTables* G;
+  const float *farend, *nearend;
+  float* out;
+  const AecListEntry* list;
+  const AecListStep* descs;
+  int num_streams, nrOfSamples, n, stride;
+  // what every Process descriptor of a batch has alike (AecSetup): handed over once per launch, so that what follows
+  // from it is worked out once, in front of the frames, as the per-stream kernel works it out in front of its sub-frames
+  int mult, nlp_mode;
+  float mu, error_threshold;
+};
+// A Process descriptor as process_call reads it: the batch's constants from the launch, the frame's own part from its
+// AecListStep (through the scalar cache).  One band, reported delays, no delay logging: what per-stream control covers.
+struct ListProcOps {
+  int32_t nsub, mult, nlp_mode;
+  float mu, error_threshold;
+  static constexpr int32_t num_high = 0, spectra = 0, agnostic = 0;
+  const __attribute__((address_space(4))) SubFrame* sub;
+};
+// one frame of one entry: far-end work, then start-up pass-through or the Process call
+template <int NP>
+__device__ __forceinline__ void list_frame(float* __restrict__ st, float* far_ring, float* __restrict__ wl, const SharedTables& T,
+                                           const AecTables* __restrict__ G, const float* __restrict__ fin,
+                                           const float* __restrict__ nin, float* __restrict__ o, int num_streams,
+                                           int nrOfSamples, int stream, int lane,
+                                           const __attribute__((address_space(4))) AecListStep* d, int mult, int nlp_mode,
+                                           float mu, float error_threshold) {
+  // (farend_work reads its frame at stream * n: hand it the entry's row moved back by that much)
+  farend_work(st, far_ring, wl, T, fin - (size_t)stream * d->far.n, num_streams, stream, d->far, lane);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  if (d->mode == 0) {  // start-up: the near end passes through
+    for (int i = lane; i < nrOfSamples; i += 64) {
+      const float v = nin[i];
+      o[i] = v;
+    }
+    return;
+  }
+  const FarOps none = {};
+  const ListProcOps ops = {d->ops.nsub, mult, nlp_mode, mu, error_threshold, d->ops.sub};
+  process_call<false, NP, false>(st, far_ring, wl, T, G, nin, o, num_streams, nrOfSamples, stream, lane, ops, nullptr, none,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+template <int NP>
+__global__ __launch_bounds__(256, NP == kNumPartNormal ? AEC_WAVES : 3) void aec_list_kernel(AecListArgs args) {
+  __shared__ SharedTables T;
+  constexpr int kWaveLds = lds_wave(NP, false);
+  __shared__ float lds[4 * kWaveLds];
+  stage_tables(T, args.G);
+  typedef const __attribute__((address_space(4))) AecListArgs* ArgsPtr;
+  typedef const __attribute__((address_space(4))) AecListEntry* EntryPtr;
+  typedef const __attribute__((address_space(4))) AecListStep* StepPtr;
+  int lane = threadIdx.x & 63;
+  int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if ((int)(blockIdx.x * 4 + wave) >= args.n) return;
+  for (int f = 0;; ++f) {
+    ArgsPtr a = (ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();  // (the by-value argument is the segment's first)
+    // read again in every frame, not kept; and what follows from the lane and wave numbers is worked out per frame
+    asm volatile("" : "+s"(a), "+s"(wave), "+v"(lane));
+    lane &= 63;  // (the range the per-stream kernels hand the shared bodies: the bodies are compiled for all their callers)
+    wave &= 3;
+    const int entry = blockIdx.x * 4 + wave;
+    const EntryPtr e = (EntryPtr)(a->list + entry);
+    if (f >= e->count) break;
+    const int stream = e->stream;
+    const size_t row = ((size_t)f * a->n + entry) * a->nrOfSamples;
+    list_frame<NP>(a->state + (size_t)stream * AecRows(NP).state_dwords, a->far_ring, lds + wave * kWaveLds, T, a->G,
+                   a->farend + row, a->nearend + row, a->out + row, a->num_streams, a->nrOfSamples, stream, lane,
+                   (StepPtr)(a->descs + (size_t)entry * a->stride + f), args.mult, args.nlp_mode, args.mu,
+                   args.error_threshold);
+    // this frame's last stores (state block, far ring) before the next frame's first loads, across the wave's lanes
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+}
+
 // aec_rdft_forward_128 / inverse_128 seam: four rows per wave.
 __global__ __launch_bounds__(256) void aec_rdft128_kernel(const float* __restrict__ src,
                                                           float* __restrict__ dst, int isgn,
@@ -1992,6 +2083,23 @@ hipError_t launch_aec_process_v(float* state, float* far_ring, const AecTables* 
   else
     hipLaunchKernelGGL((aec_process_v_kernel<kNumPartMax>), grid, dim3(256), 0, s, state, far_ring, T, nearend, out, num_streams,
                        nrOfSamples, vdesc);
+  return hipGetLastError();
+}
+
+// list calls: `n` entries (list [n]), up to `stride` frames each (descs [n][stride]), all in device memory; batch_ops:
+// the fields every Process descriptor of the batch has alike (aec_control.h, batch_proc_ops)
+hipError_t launch_aec_list(float* state, float* far_ring, const AecTables* T, const float* farend, const float* nearend,
+                           float* out, int num_streams, int nrOfSamples, int n, const AecListEntry* list,
+                           const AecListStep* descs, int stride, const ProcOps& batch_ops, int num_part, hipStream_t s) {
+  if (num_part != kNumPartNormal && num_part != kNumPartMax) return hipErrorInvalidValue;
+  if (n <= 0 || stride <= 0 || stride > kAecListMaxFrames) return hipErrorInvalidValue;
+  const dim3 grid((n + 3) / 4);
+  const AecListArgs args = {state, far_ring, T, farend, nearend, out, list, descs, num_streams, nrOfSamples, n, stride,
+                            batch_ops.mult, batch_ops.nlp_mode, batch_ops.mu, batch_ops.error_threshold};
+  if (num_part == kNumPartNormal)
+    hipLaunchKernelGGL((aec_list_kernel<kNumPartNormal>), grid, dim3(256), 0, s, args);
+  else
+    hipLaunchKernelGGL((aec_list_kernel<kNumPartMax>), grid, dim3(256), 0, s, args);
   return hipGetLastError();
 }
 

@@ -150,6 +150,22 @@ struct AecStreamStep {
 };
 static_assert(sizeof(AecStreamStep) % 8 == 0, "steps stay 8-byte aligned in their array");
 
+// List calls (AspAecBatch_RunList): one frame of one list entry -- the stream's WebRtcAec_BufferFarend call and the
+// WebRtcAec_Process call that follows it.  A launch reads them as [entry][frame] from device memory, behind the
+// launch's list of entries.
+struct AecListStep {
+  FarOps far;     // nparts == 0: the call only appends to far_pre (n == 0: not even that)
+  int32_t mode;   // as AecStreamStep::mode
+  ProcOps ops;
+};
+static_assert(sizeof(AecListStep) % 8 == 0, "steps stay 8-byte aligned in their array");
+struct AecListEntry {
+  int32_t stream;  // the batch's stream this entry steps
+  int32_t count;   // its frames in this launch (0: the wave leaves at once)
+};
+constexpr int kAecListMaxFrames = 8;  // frames of an entry that one launch carries; a longer call is cut into launches
+constexpr int kAecListSlots = 4;      // descriptor slots: list calls in flight before the next one waits
+
 // ---- delay estimation (set_config delay_logging) and the delay-agnostic mode (reported delays off) ----
 // Per stream one DelayBlock: the canonical estimator state, then what only the device needs.  In the agnostic
 // mode the stream's own far-buffer read side and system delay live in it (s.far_read .. s.system_delay): the

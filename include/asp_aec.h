@@ -250,6 +250,42 @@ int AspAecBatch_ProcessV(AspAecBatch* b, const float* nearend, float* out, int n
 int AspAecBatch_InitStream(AspAecBatch* b, int stream);
 int AspAecBatch_GetControlStream(AspAecBatch* b, int stream, AspAecControl* out);
 
+/* BufferFarend + Process of SOME streams of the batch, each by its own number of frames, in one call: what a jitter
+ * buffer delivers per tick (0 .. a few frames per stream).  For each entry i and each frame f = 0 .. counts[i] - 1 in
+ * order, stream streams[i] does WebRtcAec_BufferFarend(far[f][i], nrOfSamples) and then
+ * WebRtcAec_Process(near[f][i] -> out[f][i], nrOfSamples, msInSndCardBuf[i], 0): one reported delay per entry and
+ * call.  Results are bit-equal to the same frames fed through BufferFarend + ProcessV.
+ *   streams / counts / msInSndCardBuf [n]   0 <= n <= num_streams; a stream at most once; 0 <= counts[i] <= max_frames
+ *   farend / nearend / out   [max_frames][n][nrOfSamples]: frame f of entry i at (f * n + i) * nrOfSamples;
+ *                            out may alias nearend; nrOfSamples 80 or 160
+ *   status [n] (may be null) the OR of the reference's return values over the entry's frames (0, or -1 for a delay
+ *                            outside 0 .. 500 ms, which still processes); the call returns -1 if any is, else 0
+ * Streams not listed and entries with count 0 are left alone -- control plane, state block, far-ring slots and rows
+ * of out -- and rows f >= counts[i] of out are never written.  ASP_MEM_HOST: copies in and out, returns when done.
+ * ASP_MEM_DEVICE: enqueued on the batch's stream; streams, counts, msInSndCardBuf and status are the caller's again
+ * when the call returns.
+ * The call puts the batch under per-stream control exactly as the first ProcessV does (above: what that covers and
+ * what it refuses with ASP_ERR_STATE); the batch stays there until AspAecBatch_Init, and the uniform-argument calls
+ * keep working before, between and after list calls.  n == 0 or max_frames == 0: ASP_OK, nothing is enqueued and
+ * nothing changes.
+ * Refusals -- everything is checked before anything is enqueued or any control plane advances, the batch is left
+ * exactly as it was, the reason is in AspNs_last_error():
+ *   ASP_ERR_PARAM  a null pointer other than status; n outside 0 .. num_streams; a stream outside the batch or listed
+ *                  twice; a count outside 0 .. max_frames; a bad mem; a bad nrOfSamples
+ *   ASP_ERR_STATE  a batch that is not initialised; 32 kHz, delay logging, the delay-agnostic mode, skew
+ *                  compensation, metrics
+ * One launch carries up to ASP_AEC_LIST_MAX_FRAMES frames of every entry; a call with more is cut into launches, in
+ * frame order.  Each launch reads its entries and descriptors (176 bytes per entry and frame) from one of
+ * ASP_AEC_LIST_SLOTS slots, so calls enqueued back to back each keep their own; a launch that finds every slot still
+ * unread by the device BLOCKS the calling thread until the oldest is.  The slots -- num_streams x (8 + 8 x 176)
+ * bytes each, pinned host memory and as much device memory, 23.2 MB of each for 4096 streams -- are allocated by the
+ * first list call, not by Create.  A control-only handle accepts the call: buffers are checked for NULL only. */
+#define ASP_AEC_LIST_MAX_FRAMES 8
+#define ASP_AEC_LIST_SLOTS 4
+int AspAecBatch_RunList(AspAecBatch* b, const int32_t* streams, const int32_t* counts, int n, const float* farend,
+                        const float* nearend, float* out, int nrOfSamples, int max_frames,
+                        const int16_t* msInSndCardBuf /* [n] */, int32_t* status /* [n], may be null */, int mem);
+
 /* num_frames x (BufferFarend + Process) on [num_frames][num_streams][n] buffers: the loop of
  * test_aec_module.cpp:75-88 in one call (amortises launches; device or host memory). */
 int AspAecBatch_Run(AspAecBatch* b, const float* farend, const float* nearend, float* out,
@@ -291,6 +327,9 @@ int AspAecBatch_ExportState(AspAecBatch* b, int stream, AspAecState* out);
 int AspAecBatch_ImportState(AspAecBatch* b, int stream, const AspAecState* in);
 int AspAecBatch_GetControl(const AspAecBatch* b, AspAecControl* out);
 int AspAecBatch_Synchronize(AspAecBatch* b);
+/* The batch's hipStream_t: device-buffer calls are enqueued on it (events around them: tools/aec_list_perf.py).
+ * NULL for a control-only handle. */
+void* AspAecBatch_GetStream(AspAecBatch* b);
 /* Hand-off build of the multi-frame entry points (Run, TimedSteps) with one band and without skew compensation /
  * metrics: the plain configuration; delay logging (the process kernel forms each block's binary far / near spectra and
  * the rest of the estimator runs once per launch over all its blocks); the delay-agnostic mode (each stream's wave

@@ -26,6 +26,8 @@ def _lib():
             "AspBtBatch_macro_size": [vp],
             "AspBtBatch_Denoise": [vp, vp, vp, ip],
             "AspBtBatch_Flush": [vp, vp, ip, vp, ip],
+            "AspBtBatch_DenoiseList": [vp, vp, vp, ip, vp, vp, ip, ip],
+            "AspBtBatch_FlushList": [vp, vp, vp, ip, vp, vp, ip, ip],
             "AspBtBatch_ExportState": [vp, ip, C.POINTER(AspBtState)],
             "AspBtBatch_ImportState": [vp, ip, C.POINTER(AspBtState)],
             "AspBtBatch_Synchronize": [vp],
@@ -34,6 +36,9 @@ def _lib():
             "AspBt_kiss_fftri_batch": [vp, vp, ip, ip, ip],
         }
         _declare(lib, sig)
+        if hasattr(lib, "AspBtBatch_GetStream"):  # (absent from an earlier build loaded through ASP_AMD_LIB)
+            lib.AspBtBatch_GetStream.argtypes = [vp]
+            lib.AspBtBatch_GetStream.restype = vp
         _sig_done = True
     return lib
 
@@ -102,6 +107,54 @@ class BtBatch:
         """denoise_blocks() on device memory ([nblocks][S][macro] float32 each; see include/asp_bt.h on overlap)."""
         _check(self.lib.AspBtBatch_DenoiseBlocks(self.h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), nblocks, MEM_DEVICE),
                "AspBtBatch_DenoiseBlocks")
+
+    @staticmethod
+    def _lists(streams, counts):
+        """the two host arrays of a list call (counts None: every entry takes the call's maximum)"""
+        streams = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+            assert counts.shape == streams.shape
+        return streams, counts, (counts.ctypes.data if counts is not None else None)
+
+    def denoise_list(self, streams, counts, x, out=None):
+        """Stream-channel streams[i] advances by counts[i] macroblocks (counts None: all of them): x [K][n][macro], row i =
+        entry i, block k of row i used iff k < counts[i].  Returns the output in the same layout; blocks at or beyond
+        an entry's count keep what `out` held (a fresh array: zeros).  See include/asp_bt.h."""
+        streams, counts, cp = self._lists(streams, counts)
+        x = np.ascontiguousarray(x, np.float32)
+        assert x.ndim == 3 and x.shape[1:] == (streams.size, self.macro)
+        y = np.zeros_like(x) if out is None else out
+        assert y.dtype == np.float32 and y.shape == x.shape and y.flags.c_contiguous
+        _check(self.lib.AspBtBatch_DenoiseList(self.h, streams.ctypes.data, cp, streams.size, x.ctypes.data, y.ctypes.data,
+                                               x.shape[0], MEM_HOST), "AspBtBatch_DenoiseList")
+        return y
+
+    def denoise_list_device(self, streams, counts, in_ptr, out_ptr, max_blocks):
+        """denoise_list() on device memory ([max_blocks][n][macro] float32 each); asynchronous on the batch's stream, the
+        two lists are free for reuse on return."""
+        streams, counts, cp = self._lists(streams, counts)
+        _check(self.lib.AspBtBatch_DenoiseList(self.h, streams.ctypes.data, cp, streams.size, C.c_void_p(in_ptr),
+                                               C.c_void_p(out_ptr), max_blocks, MEM_DEVICE), "AspBtBatch_DenoiseList")
+
+    def flush_list(self, streams, hops, x, out=None):
+        """blockThreshold_flush_float of stream-channel streams[i] with hops[i] (0..7) pending hops (hops None: all of
+        them): x [n][max_hops * half], entry i uses the first hops[i] * half floats of its row.  An entry with no hop
+        still consumes its overlap tail; a stream to be left alone is not listed."""
+        streams, hops, hp = self._lists(streams, hops)
+        x = np.ascontiguousarray(x, np.float32)
+        assert x.ndim == 2 and x.shape[0] == streams.size and x.shape[1] % self.half == 0
+        y = np.zeros_like(x) if out is None else out
+        assert y.dtype == np.float32 and y.shape == x.shape and y.flags.c_contiguous
+        _check(self.lib.AspBtBatch_FlushList(self.h, streams.ctypes.data, hp, streams.size, x.ctypes.data, y.ctypes.data,
+                                             x.shape[1] // self.half, MEM_HOST), "AspBtBatch_FlushList")
+        return y
+
+    def flush_list_device(self, streams, hops, in_ptr, out_ptr, max_hops):
+        """flush_list() on device memory ([n][max_hops * half] float32 each)."""
+        streams, hops, hp = self._lists(streams, hops)
+        _check(self.lib.AspBtBatch_FlushList(self.h, streams.ctypes.data, hp, streams.size, C.c_void_p(in_ptr),
+                                             C.c_void_p(out_ptr), max_hops, MEM_DEVICE), "AspBtBatch_FlushList")
 
     def reset_stream(self, stream):
         """blockThreshold_reset of one stream-channel of the running batch."""

@@ -35,6 +35,10 @@ hipError_t launch_bt_macroblock_any(const BtAnyTables& A, float* state, const fl
                                     int frames, int threshold, int in_stride, int out_stride, hipStream_t s,
                                     unsigned long long* stamps = nullptr);
 hipError_t launch_bt_fftr_any(const BtAnyTables& A, const float* src, float* dst, int count, int inverse, hipStream_t s);
+hipError_t launch_bt_list(int win, float* state, const BtTables* T, const float* in, float* out, const int32_t* list,
+                          int n, int k0, int k1, int flush, int row, hipStream_t s);
+hipError_t launch_bt_list_any(const BtAnyTables& A, float* state, const float* in, float* out, const int32_t* list, int n,
+                              int k0, int k1, int flush, int row, hipStream_t s);
 }  // namespace aspbt
 
 namespace {
@@ -240,6 +244,22 @@ struct AspBtBatch {
   // windows), 0 = off, 1 = on.
   int flow = -1;
   HandoffSync sync;
+  // List calls (AspBtBatch_DenoiseList / FlushList): the batch's own copies of a call's lists.  A ring of kListSlots
+  // slots of 2 S words each ([streams | counts]), in pinned host memory and on the device: a call fills the next host
+  // slot, copies it to the device slot on the batch's stream and records the slot's event behind its last launch.  A
+  // slot is taken again only after that event, so every call enqueued back to back sees its own list, and the
+  // caller's arrays are free when the call returns.
+  static constexpr int kListSlots = 8;
+  int32_t* list_host = nullptr;
+  int32_t* list_dev = nullptr;
+  hipEvent_t list_ev[kListSlots] = {};
+  bool list_busy[kListSlots] = {};
+  int list_next = 0;
+  // host-memory list calls: device staging of the call's samples (grown to the largest call) and where its output
+  // lands on the host before the live part goes to the caller
+  float *list_in = nullptr, *list_out = nullptr;
+  size_t list_cap = 0;
+  std::vector<float> list_bounce;
 };
 
 namespace {
@@ -330,6 +350,12 @@ int AspBtBatch_Free(AspBtBatch* b) {
   if (b->stage_out) (void)hipFree(b->stage_out);
   if (b->ev0) (void)hipEventDestroy(b->ev0);
   if (b->ev1) (void)hipEventDestroy(b->ev1);
+  for (int i = 0; i < AspBtBatch::kListSlots; ++i)
+    if (b->list_ev[i]) (void)hipEventDestroy(b->list_ev[i]);
+  if (b->list_host) (void)hipHostFree(b->list_host);
+  if (b->list_dev) (void)hipFree(b->list_dev);
+  if (b->list_in) (void)hipFree(b->list_in);
+  if (b->list_out) (void)hipFree(b->list_out);
   if (b->side) {
     (void)hipStreamSynchronize(b->side);
     (void)hipStreamDestroy(b->side);
@@ -422,6 +448,8 @@ int AspBtBatch_Synchronize(AspBtBatch* b) {
   return bt_flow_check(b);
 }
 
+void* AspBtBatch_GetStream(AspBtBatch* b) { return b ? (void*)b->stream : nullptr; }
+
 int AspBtBatch_SetFlow(AspBtBatch* b, int mode) {
   if (!b || mode < -1 || mode > 1) return bt_fail(ASP_ERR_PARAM, "SetFlow: -1 (default), 0 (off) or 1 (on)");
   b->flow = mode;
@@ -471,6 +499,140 @@ int AspBtBatch_DenoiseBlocks(AspBtBatch* b, const float* in, float* out, int nbl
     if (rc == ASP_OK) rc = bt_flow_check(b);
   }
   return rc;
+}
+
+// ----------------------------------------------------------------- list calls (asp_bt.h)
+// The next slot of the batch's list ring, free for reuse: the launches that read it last have finished.
+static int bt_list_slot_take(AspBtBatch* b, int* slot) {
+  const size_t words = (size_t)AspBtBatch::kListSlots * 2 * (size_t)b->S;
+  if (!b->list_host) BT_TRY(hipHostMalloc((void**)&b->list_host, words * sizeof(int32_t), hipHostMallocDefault));
+  if (!b->list_dev) BT_TRY(hipMalloc((void**)&b->list_dev, words * sizeof(int32_t)));
+  const int k = b->list_next;
+  if (!b->list_ev[k]) BT_TRY(hipEventCreateWithFlags(&b->list_ev[k], hipEventDisableTiming));
+  if (b->list_busy[k]) {
+    BT_TRY(hipEventSynchronize(b->list_ev[k]));
+    b->list_busy[k] = false;
+  }
+  *slot = k;
+  return ASP_OK;
+}
+
+// Both list calls.  flush == 0: DenoiseList, `counts` macroblocks of at most `max_count`, rows of in / out are
+// [max_count][n][macro]; flush: FlushList, `counts` pending hops of at most `max_count` <= 7, rows [n][max_count * half].
+// Everything is validated before anything is enqueued or allocated.
+static int bt_list_run(AspBtBatch* b, const char* who, bool flush, const int32_t* streams, const int32_t* counts, int n,
+                       const float* in, float* out, int max_count, int mem) {
+  AspDeviceScope dev_scope_;
+  char msg[160];
+#define LIST_FAIL(text)                             \
+  do {                                              \
+    snprintf(msg, sizeof msg, "%s: %s", who, text); \
+    return bt_fail(ASP_ERR_PARAM, msg);             \
+  } while (0)
+  if (!b) LIST_FAIL("null batch handle");
+  if (n < 0 || n > b->S) LIST_FAIL("n must be 0 .. num_streams");
+  if (max_count < 0) LIST_FAIL(flush ? "max_hops must be 0 .. 7" : "max_blocks must not be negative");
+  if (flush && max_count > 7) LIST_FAIL("max_hops must be 0 .. 7");
+  if (mem != ASP_MEM_HOST && mem != ASP_MEM_DEVICE) LIST_FAIL("mem must be ASP_MEM_HOST or ASP_MEM_DEVICE");
+  if ((!in || !out) && n > 0 && max_count > 0) LIST_FAIL("null samples");
+  if (n > 0 && !streams) LIST_FAIL("null stream list");
+  const size_t row = flush ? (size_t)max_count * b->half : (size_t)b->macro;  // floats of one row
+  const size_t total = flush ? (size_t)n * row : (size_t)max_count * n * row;  // floats of in, and of out
+  if (in != out && total > 0) {  // out == in works in place; any other shared byte is refused
+    const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out, span = total * sizeof(float);
+    if (i0 < o0 + span && o0 < i0 + span) LIST_FAIL("in and out overlap (only out == in is allowed)");
+  }
+  std::vector<unsigned char> seen((size_t)b->S, 0);
+  int maxc = 0;  // the longest entry
+  for (int i = 0; i < n; ++i) {
+    const int s = streams[i];
+    if (s < 0 || s >= b->S) LIST_FAIL("a listed stream is outside the batch");
+    if (seen[s]) LIST_FAIL("a stream is listed twice (two workgroups on one state would race)");
+    seen[s] = 1;
+    const int c = counts ? counts[i] : max_count;
+    if (c < 0 || c > max_count) LIST_FAIL(flush ? "hops outside 0 .. max_hops" : "a count is outside 0 .. max_blocks");
+    if (c > maxc) maxc = c;
+  }
+#undef LIST_FAIL
+  // a flush entry with no hop still consumes its overlap tail: only an empty list is a flush that does nothing
+  if (n == 0 || (!flush && maxc == 0)) return ASP_OK;
+  BT_TRY(dev_scope_.select(b->device));
+
+  const size_t used = flush ? total : (size_t)maxc * n * row;  // floats of in / out the launches can touch
+  const float* din = in;
+  float* dout = out;
+  if (mem == ASP_MEM_HOST && used > 0) {
+    if (b->list_cap < used) {
+      BT_TRY(hipStreamSynchronize(b->stream));  // an earlier call may still run on the old buffers
+      if (b->list_in) (void)hipFree(b->list_in);
+      if (b->list_out) (void)hipFree(b->list_out);
+      b->list_in = b->list_out = nullptr;
+      b->list_cap = 0;
+      BT_TRY(hipMalloc((void**)&b->list_in, used * sizeof(float)));
+      BT_TRY(hipMalloc((void**)&b->list_out, used * sizeof(float)));
+      b->list_cap = used;
+    }
+    b->list_bounce.resize(used);
+  }
+  int slot = 0;
+  int rc = bt_list_slot_take(b, &slot);
+  if (rc) return rc;
+  int32_t* hl = b->list_host + (size_t)slot * 2 * b->S;
+  int32_t* dl = b->list_dev + (size_t)slot * 2 * b->S;
+  for (int i = 0; i < n; ++i) {
+    hl[i] = streams[i];
+    hl[n + i] = counts ? counts[i] : max_count;
+  }
+  BT_TRY(hipMemcpyAsync(dl, hl, (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+  b->list_busy[slot] = true;  // (from here on the slot's event is recorded, whatever fails below)
+  b->list_next = (slot + 1) % AspBtBatch::kListSlots;
+  hipError_t e = hipSuccess;
+  if (mem == ASP_MEM_HOST && used > 0) {
+    e = hipMemcpyAsync(b->list_in, in, used * sizeof(float), hipMemcpyHostToDevice, b->stream);
+    din = b->list_in;
+    dout = b->list_out;
+  }
+  if (flush) {
+    if (e == hipSuccess)
+      e = b->any ? launch_bt_list_any(b->any_tables, b->state, din, dout, dl, n, 0, 0, 1, (int)row, b->stream)
+                 : launch_bt_list(b->win, b->state, b->tables, din, dout, dl, n, 0, 0, 1, (int)row, b->stream);
+  } else {
+    // launches of at most kHandoffMaxSteps macroblocks of each entry, in block order
+    for (int k0 = 0; k0 < maxc && e == hipSuccess; k0 += kHandoffMaxSteps) {
+      const int k1 = k0 + kHandoffMaxSteps;
+      e = b->any ? launch_bt_list_any(b->any_tables, b->state, din, dout, dl, n, k0, k1, 0, 0, b->stream)
+                 : launch_bt_list(b->win, b->state, b->tables, din, dout, dl, n, k0, k1, 0, 0, b->stream);
+    }
+  }
+  const hipError_t er = hipEventRecord(b->list_ev[slot], b->stream);
+  if (e == hipSuccess) e = er;
+  if (e != hipSuccess) return bt_fail(ASP_ERR_HIP, "enqueuing a list call", e);
+  if (mem != ASP_MEM_HOST) return ASP_OK;
+  if (used > 0) BT_TRY(hipMemcpyAsync(b->list_bounce.data(), b->list_out, used * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+  BT_TRY(hipStreamSynchronize(b->stream));
+  // only what the entries produced may change in the caller's `out`
+  for (int i = 0; i < n; ++i) {
+    const int c = counts ? counts[i] : max_count;
+    if (flush) {
+      memcpy(out + (size_t)i * row, b->list_bounce.data() + (size_t)i * row, (size_t)c * b->half * sizeof(float));
+    } else {
+      for (int k = 0; k < c; ++k) {
+        const size_t off = ((size_t)k * n + i) * row;
+        memcpy(out + off, b->list_bounce.data() + off, row * sizeof(float));
+      }
+    }
+  }
+  return ASP_OK;
+}
+
+int AspBtBatch_DenoiseList(AspBtBatch* b, const int32_t* streams, const int32_t* counts, int n, const float* in, float* out,
+                           int max_blocks, int mem) {
+  return bt_list_run(b, "DenoiseList", false, streams, counts, n, in, out, max_blocks, mem);
+}
+
+int AspBtBatch_FlushList(AspBtBatch* b, const int32_t* streams, const int32_t* hops, int n, const float* in, float* out,
+                         int max_hops, int mem) {
+  return bt_list_run(b, "FlushList", true, streams, hops, n, in, out, max_hops, mem);
 }
 
 int AspBtBatch_TimedSteps(AspBtBatch* b, const float* in, float* out, int blocks_in_ring,

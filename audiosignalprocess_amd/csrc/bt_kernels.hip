@@ -255,11 +255,11 @@ __device__ __forceinline__ float block_sum_dispatch(int c, const float* tile, in
 // --------------------------------------------------------------------------
 // One macroblock (frames = 8, threshold = 1) or one flush (frames < 8, threshold = 0)
 // of every stream.
+// The body: `st` is the stream-channel's state block, x / y its samples in and out.
 template <int N>
-__global__ __launch_bounds__(N / 2) void bt_macroblock_kernel(
-    float* __restrict__ state, const BtTables* __restrict__ Tb, const float* __restrict__ in,
-    float* __restrict__ out, int frames, int threshold, int in_stride, int out_stride,
-    unsigned long long* __restrict__ stamps) {
+__device__ __forceinline__ void bt_macroblock_body(float* __restrict__ st, const BtTables* __restrict__ Tb,
+                                                   const float* __restrict__ x, float* __restrict__ y, int frames,
+                                                   int threshold, unsigned long long* __restrict__ stamps) {
   constexpr int NC = N / 2, HALF = N / 2, NB = N / 2 + 1;
   // diagnostic phase stamps (never enabled by the product entry points): workgroup 0, thread 0
 #define BT_STAMP(k)                                                                   \
@@ -273,10 +273,6 @@ __global__ __launch_bounds__(N / 2) void bt_macroblock_kernel(
   float* sure = reinterpret_cast<float*>(thre + 8 * NB);  // [NCOL][15]
 
   const int tid = threadIdx.x;
-  const int stream = blockIdx.x;
-  float* st = state + (size_t)stream * kStateFloats;
-  const float* x = in + (size_t)stream * in_stride;
-  float* y = out + (size_t)stream * out_stride;
   const BtSize& P = N == 1024 ? Tb->s1024 : Tb->s256;
   const float* hann = N == 1024 ? Tb->hann1024 : Tb->hann256;
   const cpx* tw_f = reinterpret_cast<const cpx*>(N == 1024 ? Tb->tw1024_f : Tb->tw256_f);
@@ -448,6 +444,40 @@ __global__ __launch_bounds__(N / 2) void bt_macroblock_kernel(
 #undef BT_STAMP
 }
 
+template <int N>
+__global__ __launch_bounds__(N / 2) void bt_macroblock_kernel(
+    float* __restrict__ state, const BtTables* __restrict__ Tb, const float* __restrict__ in,
+    float* __restrict__ out, int frames, int threshold, int in_stride, int out_stride,
+    unsigned long long* __restrict__ stamps) {
+  const int stream = blockIdx.x;
+  bt_macroblock_body<N>(state + (size_t)stream * kStateFloats, Tb, in + (size_t)stream * in_stride,
+                        out + (size_t)stream * out_stride, frames, threshold, stamps);
+}
+
+// The list form (AspBtBatch_DenoiseList / FlushList, asp_bt.h): workgroup i takes entry i of the device copy of the
+// call's list, list = [streams[n] | counts[n]].  Denoise (flush == 0): the entry's macroblocks k0 <= k < min(count, k1),
+// in order, block k of row i at (k n + i) * macro of in / out; the two tails go from block to block through the
+// state, behind a workgroup barrier.  Flush: `count` pending hops without thresholding, row i at i * row; no hop
+// still clears the overlap tail (the body with frames = 0).  Nothing past an entry's count is read or written.
+template <int N>
+__global__ __launch_bounds__(N / 2) void bt_macroblock_list_kernel(
+    float* __restrict__ state, const BtTables* __restrict__ Tb, const float* __restrict__ in, float* __restrict__ out,
+    const int32_t* __restrict__ list, int n, int k0, int k1, int flush, int row) {
+  const int i = blockIdx.x;
+  const int stream = list[i], count = list[n + i];
+  float* st = state + (size_t)stream * kStateFloats;
+  if (flush) {
+    bt_macroblock_body<N>(st, Tb, in + (size_t)i * row, out + (size_t)i * row, count, 0, nullptr);
+    return;
+  }
+  const int kend = count < k1 ? count : k1;
+  for (int k = k0; k < kend; ++k) {
+    const size_t off = ((size_t)k * n + i) * (8 * (N / 2));
+    bt_macroblock_body<N>(st, Tb, in + off, out + off, 8, 1, nullptr);
+    __syncthreads();  // the tails this block left in the state, and the LDS tiles, before the next block
+  }
+}
+
 // --------------------------------------------------------------------------
 // Any even window of 4 .. 2048 samples (20 ms at 16 kHz = 320, 50 ms = 800, 10 / 40 ms at 48 kHz = 480 / 1920, ...):
 // the same phases with run-time sizes and kiss_fft's mixed-radix plan -- radix 4, 2, 3, 5 and the generic
@@ -585,9 +615,9 @@ __device__ __forceinline__ void any_stages(cpx* work, const cpx* __restrict__ tw
 
 // SQW: columns of the squared-real table (32 for windows of up to 1024 samples: at most 31 macro-columns; else 64)
 template <int THREADS, int SQW, bool GENERIC>
-__global__ __launch_bounds__(THREADS) void bt_macroblock_any_kernel(
-    float* __restrict__ state, const BtAnyTables* __restrict__ Ap, const float* __restrict__ in, float* __restrict__ out, int frames,
-    int threshold, int in_stride, int out_stride, unsigned long long* __restrict__ stamps) {
+__device__ __forceinline__ void bt_macroblock_any_body(float* __restrict__ st, const BtAnyTables* __restrict__ Ap,
+                                                       const float* __restrict__ x, float* __restrict__ y, int frames,
+                                                       int threshold, unsigned long long* __restrict__ stamps) {
   const BtAnyTables& A = *Ap;  // the plan stays in memory (scalar loads where it is read)
   // diagnostic phase stamps (never enabled by the product entry points): workgroup 0, thread 0
 #define BTA_STAMP(k) \
@@ -606,10 +636,6 @@ __global__ __launch_bounds__(THREADS) void bt_macroblock_any_kernel(
   float* sure = sq_in_thre ? after : after + 128 * SQW;  // [NCOL][15], then 16 spare, then 4 x (128 + 64)
   float* stage = sure + NCOL * 15 + 16 + (THREADS / 64) * (128 + 64);  // [HALF] new output tail
   const int tid = threadIdx.x;
-  const int stream = blockIdx.x;
-  float* st = state + (size_t)stream * kAnyStateFloats;
-  const float* x = in + (size_t)stream * in_stride;
-  float* y = out + (size_t)stream * out_stride;
   const BtSize& P = A.P;
   const cpx* tw_f = reinterpret_cast<const cpx*>(A.tw_f);
   const cpx* tw_i = reinterpret_cast<const cpx*>(A.tw_i);
@@ -821,6 +847,36 @@ __global__ __launch_bounds__(THREADS) void bt_macroblock_any_kernel(
 #undef BTA_STAMP
 }
 
+template <int THREADS, int SQW, bool GENERIC>
+__global__ __launch_bounds__(THREADS) void bt_macroblock_any_kernel(
+    float* __restrict__ state, const BtAnyTables* __restrict__ Ap, const float* __restrict__ in, float* __restrict__ out, int frames,
+    int threshold, int in_stride, int out_stride, unsigned long long* __restrict__ stamps) {
+  const int stream = blockIdx.x;
+  bt_macroblock_any_body<THREADS, SQW, GENERIC>(state + (size_t)stream * kAnyStateFloats, Ap, in + (size_t)stream * in_stride,
+                                                out + (size_t)stream * out_stride, frames, threshold, stamps);
+}
+
+// The list form for any window: as bt_macroblock_list_kernel.
+template <int THREADS, int SQW, bool GENERIC>
+__global__ __launch_bounds__(THREADS) void bt_macroblock_any_list_kernel(
+    float* __restrict__ state, const BtAnyTables* __restrict__ Ap, const float* __restrict__ in, float* __restrict__ out,
+    const int32_t* __restrict__ list, int n, int k0, int k1, int flush, int row) {
+  const int i = blockIdx.x;
+  const int stream = list[i], count = list[n + i];
+  float* st = state + (size_t)stream * kAnyStateFloats;
+  if (flush) {
+    bt_macroblock_any_body<THREADS, SQW, GENERIC>(st, Ap, in + (size_t)i * row, out + (size_t)i * row, count, 0, nullptr);
+    return;
+  }
+  const int macro = 8 * Ap->nc;
+  const int kend = count < k1 ? count : k1;
+  for (int k = k0; k < kend; ++k) {
+    const size_t off = ((size_t)k * n + i) * macro;
+    bt_macroblock_any_body<THREADS, SQW, GENERIC>(st, Ap, in + off, out + off, 8, 1, nullptr);
+    __syncthreads();
+  }
+}
+
 // kiss_fftr / kiss_fftri seam for any even length: one workgroup per row
 __global__ __launch_bounds__(kAnyThreads) void bt_fftr_any_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                                    int inverse, const BtAnyTables* __restrict__ Ap) {
@@ -947,6 +1003,8 @@ hipError_t launch_bt_macroblock8_q4(float* state, const BtTables* T, const float
                                     int in_stride, int out_stride, hipStream_t s);
 hipError_t launch_bt_fftr8(const float* src, float* dst, int count, int inverse, const BtTables* T,
                            hipStream_t s);
+hipError_t launch_bt_macroblock8_list(bool q4, float* state, const BtTables* T, const float* in, float* out,
+                                      const int32_t* list, int n, int groups, int k0, int k1, hipStream_t s);
 
 size_t macroblock_lds_bytes(int n) {
   const int nb = n / 2 + 1, ncol = (n - 1) / 2 / 16;
@@ -1052,6 +1110,83 @@ hipError_t launch_bt_macroblock_any(const BtAnyTables& A, float* state, const fl
   else
     BT_ANY_LAUNCH(256, 16);
 #undef BT_ANY_LAUNCH
+  return hipGetLastError();
+}
+
+// List launches (AspBtBatch_DenoiseList / FlushList): `list` is the device copy [streams[n] | counts[n]] of the call's
+// list.  Denoise (flush == 0): macroblocks k0 <= k < k1 of every entry that has them, in / out [..][n][macro]; flush:
+// rows of `row` floats.  The plain list kernels serve everything; whole macroblocks of the 1024- and 256-sample
+// windows on 8-byte aligned samples take the tuned kernel's list form (256 samples: four entries per workgroup, the
+// entries the last group lacks masked).
+hipError_t launch_bt_list(int win, float* state, const BtTables* T, const float* in, float* out, const int32_t* list,
+                          int n, int k0, int k1, int flush, int row, hipStream_t s) {
+  if (!flush && ((uintptr_t)in & 7) == 0 && ((uintptr_t)out & 7) == 0 && !getenv("ASP_BT_OLD_KERNEL"))
+    return launch_bt_macroblock8_list(win == 256, state, T, in, out, list, n, win == 256 ? (n + 3) / 4 : n, k0, k1, s);
+  const size_t lds = macroblock_lds_bytes(win);
+  if (win == 1024) {
+    static bool attr_set[64] = {};  // per device, as in launch_bt_macroblock
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bt_macroblock_list_kernel<1024>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(bt_macroblock_list_kernel<1024>, dim3(n), dim3(512), lds, s, state, T, in, out, list, n, k0,
+                       k1, flush, row);
+  } else {
+    hipLaunchKernelGGL(bt_macroblock_list_kernel<256>, dim3(n), dim3(128), lds, s, state, T, in, out, list, n, k0,
+                       k1, flush, row);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_bt_list_any(const BtAnyTables& A, float* state, const float* in, float* out, const int32_t* list, int n,
+                              int k0, int k1, int flush, int row, hipStream_t s) {
+  // the shapes of launch_bt_macroblock_any
+  const int sqw = A.ncol <= 15 ? 16 : A.ncol <= 31 ? 32 : 64;
+  const int threads = A.nc >= 192 ? 512 : 256;
+  const size_t tile = (size_t)8 * (A.nc + 1) * sizeof(cpx), sq = (size_t)128 * sqw * sizeof(float);
+  const size_t lds = 2 * tile + (size_t)A.nc * sizeof(cpx) + (tile >= sq ? 0 : sq) +
+                     (size_t)(A.ncol * 15 + 16 + (threads / 64) * (128 + 64) + A.nc) * sizeof(float);
+  static bool attr_set[64] = {};  // per device
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
+    const int max_lds = 156 * 1024;
+    hipError_t e = hipSuccess;
+    const void* big[] = {reinterpret_cast<const void*>(bt_macroblock_any_list_kernel<512, 64, false>),
+                         reinterpret_cast<const void*>(bt_macroblock_any_list_kernel<512, 64, true>),
+                         reinterpret_cast<const void*>(bt_macroblock_any_list_kernel<512, 32, false>),
+                         reinterpret_cast<const void*>(bt_macroblock_any_list_kernel<512, 32, true>)};
+    for (const void* f : big)
+      if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    if (e != hipSuccess) return e;
+    attr_set[dev] = true;
+  }
+  bool generic = false;
+  for (int q = 0; q < A.nfac; ++q) generic |= A.fac[2 * q] > 5;
+#define BT_ANY_LIST(TH, SQ)                                                                                          \
+  do {                                                                                                               \
+    if (generic)                                                                                                     \
+      hipLaunchKernelGGL((bt_macroblock_any_list_kernel<TH, SQ, true>), dim3(n), dim3(TH), lds, s, state, A.self, in, out, \
+                         list, n, k0, k1, flush, row);                                                            \
+    else                                                                                                             \
+      hipLaunchKernelGGL((bt_macroblock_any_list_kernel<TH, SQ, false>), dim3(n), dim3(TH), lds, s, state, A.self, in, out, \
+                         list, n, k0, k1, flush, row);                                                            \
+  } while (0)
+  if (threads == 512 && sqw == 64)
+    BT_ANY_LIST(512, 64);
+  else if (threads == 512 && sqw == 32)
+    BT_ANY_LIST(512, 32);
+  else if (threads == 512)
+    BT_ANY_LIST(512, 16);
+  else if (sqw == 32)
+    BT_ANY_LIST(256, 32);
+  else
+    BT_ANY_LIST(256, 16);
+#undef BT_ANY_LIST
   return hipGetLastError();
 }
 

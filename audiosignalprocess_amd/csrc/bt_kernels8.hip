@@ -568,20 +568,44 @@ __device__ __forceinline__ void st2_sc1(float* p, f32x2 v) {
   __hip_atomic_store((bt_gu64*)p, __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool Q4, bool FLOW>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, BT8_WAVES))) void bt_macroblock8_kernel(
+// The list form (LIST; bt_macroblock8_list_kernel): the rows of in / out a workgroup takes are still blockIdx.x (Q4:
+// 4 blockIdx.x .. + 3), but the stream-channel behind a row comes from the call's list, and at Q4 a row may be dead
+// -- past the end of the list, or a stream-channel past its own count while its neighbours go on.  A dead row loads
+// zeros and stores nothing, neither samples nor state: the four 128-point transforms of the interleaved network, the
+// macro-columns and the edge lanes of a stream-channel never mix with a neighbour's, so whatever a dead row computes
+// (0 / 0 in its block energies) stays in its own lanes.
+struct BtListWg {
+  int s[4];      // the stream-channels of the workgroup's rows (Q4: four; else s[0]); 0 where there is none
+  unsigned live;  // bit q: this block of row q exists
+};
+__device__ __forceinline__ int pick4(const int (&a)[4], int q) { return q == 0 ? a[0] : q == 1 ? a[1] : q == 2 ? a[2] : a[3]; }
+
+template <bool Q4, bool FLOW, bool LIST>
+__device__ __forceinline__ void bt_macroblock8_body(
     float* __restrict__ state, const BtTables* __restrict__ Tb, const float* __restrict__ in,
-    float* __restrict__ out, int in_stride, int out_stride, unsigned long long* __restrict__ stamps, BtFlowArgs fa) {
+    float* __restrict__ out, int in_stride, int out_stride, unsigned long long* __restrict__ stamps, const BtFlowArgs& fa,
+    const BtListWg& lw) {
+  static_assert(!(FLOW && LIST), "the list form walks inside the workgroup: no hand-off counters");
   __shared__ __align__(256) cpx coef[8 * ROW];     // [frame][bin]; a wave's row is also its exchange buffer
   __shared__ __align__(16) float sq[128 * SQS];    // squared normalised real parts; later the OLA halves
   __shared__ float sure[NCOL * SUS + 15];          // [macro-column][segmentation], then a_const of the 15 segmentations
   __shared__ __align__(16) cpx twl[kTwLds];        // kiss_fft twiddles 0..383 (forward)
   BT8_STAMP(0)
-  const int tid = threadIdx.x, lane = tid & 63;
+  int tid_ = threadIdx.x;
+  // the list form runs the body in a loop: what derives from the lane is formed anew in every block, as in the
+  // one-block kernels (kept across the loop it would take the registers the body needs and spill)
+  if constexpr (LIST) asm volatile("" : "+v"(tid_));
+  const int tid = tid_, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: the phase switches are scalar branches
   constexpr int HALFV = Q4 ? 128 : HALF, NCOLV = Q4 ? 4 * NCOLQ : NCOL;
   // the stream whose samples this lane loads (Q4: input 4 n' + s of the interleaved array sits on lanes with lane & 3 = s)
-  const int stream = Q4 ? 4 * blockIdx.x + (lane & 3) : blockIdx.x;
+  const int rowl = Q4 ? 4 * blockIdx.x + (lane & 3) : blockIdx.x;  // its row of in / out
+  int stream = rowl;
+  bool live = true;
+  if constexpr (LIST) {
+    stream = Q4 ? pick4(lw.s, lane & 3) : lw.s[0];
+    if constexpr (Q4) live = (lw.live >> (lane & 3)) & 1u;
+  }
   float* st = state + (size_t)stream * kStateFloats;
   const float* in_prev = in;  // hand-off build: the previous macroblock's input (steps after the launch's first)
   unsigned flow_want = 0;
@@ -597,8 +621,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, 
     flow_first = j == 0;
     flow_last = j + 1 == gridDim.y;
   }
-  const float* x = in + (size_t)stream * in_stride;
-  float* y = out + (size_t)stream * out_stride;
+  const float* x = in + (size_t)rowl * in_stride;
+  float* y = out + (size_t)rowl * out_stride;
   const BtSize& P = Q4 ? Tb->s256 : Tb->s1024;
   const cpx* tw = reinterpret_cast<const cpx*>(Tb->tw1024_f);
   const cpx* sup = reinterpret_cast<const cpx*>(Q4 ? Tb->sup256_f : Tb->sup1024_f);
@@ -623,7 +647,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, 
       const float* tail_src = (FLOW && !flow_first) ? in_prev + (size_t)stream * in_stride + 7 * HALFV + 2 * n
                                                     : st + kOffInTail + 2 * n;
       const float* src = (wave == 0 && (j & 1) == 0) ? tail_src : x + HALFV * (wave - 1) + 2 * n;
-      s[j] = *reinterpret_cast<const f32x2*>(src);
+      if constexpr (LIST && Q4) {
+        s[j] = f32x2{0.0f, 0.0f};
+        if (live) s[j] = *reinterpret_cast<const f32x2*>(src);
+      } else {
+        s[j] = *reinterpret_cast<const f32x2*>(src);
+      }
       hw[j] = hann2[n];
     }
     if (tid < kTwLds) twl[tid] = tw[tid];
@@ -654,6 +683,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, 
   // kernel, behind the hand-off: the launch's FIRST step reads the state's copy, and nothing but the chain of
   // sequence waits orders this workgroup behind that one
   if constexpr (FLOW) {
+  } else if constexpr (Q4 && LIST) {
+    const int q = wave >> 1;  // two waves carry a row's half window
+    if ((lw.live >> q) & 1u)
+      state[(size_t)pick4(lw.s, q) * kStateFloats + kOffInTail + (tid & 127)] =
+          in[((size_t)4 * blockIdx.x + q) * in_stride + 7 * HALFV + (tid & 127)];
   } else if constexpr (Q4) {
     const size_t sq4 = (size_t)4 * blockIdx.x + (tid >> 7);
     state[sq4 * kStateFloats + kOffInTail + (tid & 127)] = in[sq4 * in_stride + 7 * HALFV + (tid & 127)];
@@ -816,6 +850,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, 
           tail[j] = Q4 ? ld2_sc1(state + (g4 + j) * kStateFloats + kOffOutTail + 2 * lane)
                        : ld2_sc1(st + kOffOutTail + 2 * (lane + 64 * j));
       }
+    } else if constexpr (Q4 && LIST) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        tail[j] = f32x2{0.0f, 0.0f};
+        if ((lw.live >> j) & 1u)
+          tail[j] = *reinterpret_cast<const f32x2*>(state + (size_t)lw.s[j] * kStateFloats + kOffOutTail + 2 * lane);
+      }
     } else {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -862,13 +903,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, 
         acc = f32x2{0.0f, 0.0f} + pr;
       }
       acc = acc + v[2 * q] * inv_n;
-      *reinterpret_cast<f32x2*>(out + (g4 + q) * out_stride + HALFV * wave + 2 * lane) = acc;
+      if constexpr (LIST) {
+        if ((lw.live >> q) & 1u) *reinterpret_cast<f32x2*>(out + (g4 + q) * out_stride + HALFV * wave + 2 * lane) = acc;
+      } else {
+        *reinterpret_cast<f32x2*>(out + (g4 + q) * out_stride + HALFV * wave + 2 * lane) = acc;
+      }
     }
     if (wave == 7) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float* dst = state + (g4 + q) * kStateFloats + kOffOutTail + 2 * lane;
-        if constexpr (FLOW) st2_sc1(dst, f32x2{0.0f, 0.0f} + v[2 * q + 1]);
+        if constexpr (LIST) {
+          dst = state + (size_t)lw.s[q] * kStateFloats + kOffOutTail + 2 * lane;
+          if ((lw.live >> q) & 1u) *reinterpret_cast<f32x2*>(dst) = f32x2{0.0f, 0.0f} + v[2 * q + 1];
+        } else if constexpr (FLOW) st2_sc1(dst, f32x2{0.0f, 0.0f} + v[2 * q + 1]);
         else *reinterpret_cast<f32x2*>(dst) = f32x2{0.0f, 0.0f} + v[2 * q + 1];
       }
       if constexpr (FLOW) {  // publish the four stream-channels' macroblock: the tail stores drained first
@@ -925,6 +973,62 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, 
   }
   BT8_STAMP(10)
   BT8_WSTAMP(3)
+}
+
+template <bool Q4, bool FLOW>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, BT8_WAVES))) void bt_macroblock8_kernel(
+    float* __restrict__ state, const BtTables* __restrict__ Tb, const float* __restrict__ in,
+    float* __restrict__ out, int in_stride, int out_stride, unsigned long long* __restrict__ stamps, BtFlowArgs fa) {
+  const BtListWg none = {};
+  bt_macroblock8_body<Q4, FLOW, false>(state, Tb, in, out, in_stride, out_stride, stamps, fa, none);
+}
+
+// The list form (AspBtBatch_DenoiseList): `list` = [streams[n] | counts[n]], the device copy of the call's list.  A
+// workgroup takes entry blockIdx.x (Q4: entries 4 blockIdx.x .. + 3, as many as the list has) and walks the entry's
+// macroblocks k0 <= k < min(count, k1) itself, in order; block k of row i is at (k n + i) * macro of in / out.  The
+// two tails go from block to block through the state, behind the workgroup barrier that closes a block (it also
+// frees the LDS tiles): no step counter, no waiting on another workgroup, and no read of a previous block's input
+// slot, which out == in has overwritten by then.  Q4: the walk is as long as the longest of the four counts; a
+// stream-channel past its own is a dead row of the body.
+struct BtListArgs {
+  const int32_t* list;
+  int n, k0, k1;
+};
+template <bool Q4>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BT8_WAVES, BT8_WAVES))) void bt_macroblock8_list_kernel(
+    float* __restrict__ state, const BtTables* __restrict__ Tb, const float* __restrict__ in,
+    float* __restrict__ out, BtListArgs la) {
+  constexpr int ROWS = Q4 ? 4 : 1, MACRO = Q4 ? 8 * 128 : 8 * HALF;
+  const int e0 = ROWS * blockIdx.x;
+  BtListWg lw = {};
+  // blocks of this launch per row, a byte each (a launch carries at most 255 blocks of an entry; the host sends 64):
+  // one scalar register instead of four across the walk
+  unsigned todo = 0u;
+  int steps = 0;
+#pragma unroll
+  for (int q = 0; q < ROWS; ++q) {
+    int c = 0;
+    if (e0 + q < la.n) {  // wave-uniform: scalar loads, and no list read past its end
+      lw.s[q] = __builtin_amdgcn_readfirstlane(la.list[e0 + q]);
+      c = __builtin_amdgcn_readfirstlane(la.list[la.n + e0 + q]);
+    }
+    c = max(min(c, la.k1) - la.k0, 0);
+    todo |= (unsigned)c << (8 * q);
+    steps = max(steps, c);
+  }
+  const BtFlowArgs none = {{nullptr, nullptr}, 0u, 0, 1, 0u};
+  for (int j = 0; j < steps; ++j) {
+    const int k = la.k0 + j;
+    lw.live = 0u;
+#pragma unroll
+    for (int q = 0; q < ROWS; ++q) lw.live |= (unsigned)((unsigned)j < ((todo >> (8 * q)) & 255u)) << q;
+    const size_t off = (size_t)k * la.n * MACRO;
+    int zero = 0;
+    asm volatile("" : "+s"(zero));  // likewise the table loads: issued in every block, not held across the loop
+    const BtTables* tb = reinterpret_cast<const BtTables*>(reinterpret_cast<const char*>(Tb) + zero);
+    bt_macroblock8_body<Q4, false, true>(state, tb, in + off, out + off, MACRO, MACRO, nullptr, none, lw);
+    __syncthreads();
+  }
 }
 
 // kiss_fftr / kiss_fftri seam for N = 1024 through the same wave routines: one wave per row.
@@ -1005,6 +1109,18 @@ hipError_t launch_bt_macroblock8_flow(bool q4, float* state, const BtTables* T, 
   else
     hipLaunchKernelGGL((bt_macroblock8_kernel<false, true>), dim3(num_streams, steps), dim3(512), 0, s, state, T, in, out,
                        stride, stride, (unsigned long long*)nullptr, fa);
+  return hipGetLastError();
+}
+
+// The list form: `groups` workgroups, one entry each (q4: four entries each, groups = ceil(n / 4): the entries the
+// last group lacks are dead rows).  in / out 8-byte aligned.
+hipError_t launch_bt_macroblock8_list(bool q4, float* state, const BtTables* T, const float* in, float* out,
+                                      const int32_t* list, int n, int groups, int k0, int k1, hipStream_t s) {
+  const BtListArgs la = {list, n, k0, k1};
+  if (q4)
+    hipLaunchKernelGGL((bt_macroblock8_list_kernel<true>), dim3(groups), dim3(512), 0, s, state, T, in, out, la);
+  else
+    hipLaunchKernelGGL((bt_macroblock8_list_kernel<false>), dim3(groups), dim3(512), 0, s, state, T, in, out, la);
   return hipGetLastError();
 }
 

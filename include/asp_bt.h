@@ -96,9 +96,52 @@ int AspBtBatch_Denoise(AspBtBatch* b, const float* in, float* out, int mem);
  * later complete, starts from a cleared tail) and leaves the input history
  * alone (the pending hops stay pending and are fed again with their macroblock). */
 int AspBtBatch_Flush(AspBtBatch* b, const float* in, int hops, float* out, int mem);
+
+/* Macroblocks of SOME stream-channels of the batch: list entry i is stream-channel streams[i], which advances by
+ * counts[i] macroblocks (counts == NULL: max_blocks each).  in / out: [max_blocks][n][macro_size] float32, row i =
+ * entry i (the slot layout of AspBtBatch_DenoiseBlocks with n in place of num_streams); block k of row i is read and
+ * written iff k < counts[i]: the rest of in is never interpreted, the rest of out never written.  Streams not listed,
+ * and entries with count 0, are untouched: both tails, bit for bit.  What a server needs whose streams joined at
+ * different times: the reference feeds hops of half a window and a macroblock completes every eighth hop, so at one
+ * tick an eighth of the streams have a macroblock, a late one has two, most have none.  Results, and the state left
+ * behind, are bit for bit those of the lock-step calls fed the same macroblocks per stream.
+ *
+ * AspBtBatch_FlushList: entry i flushes stream-channel streams[i] with hops[i] (0 .. 7) pending hops (hops == NULL:
+ * max_hops each); in / out: [n][max_hops * half], entry i uses the first hops[i] * half floats of its row and the
+ * rest of its out row is not written.  Per entry it is exactly AspBtBatch_Flush: no thresholding, the overlap tail
+ * is consumed, the input history is left alone.  An entry with hops[i] == 0 still consumes its overlap tail (hops == 0
+ * consumes the tail, as AspBtBatch_Flush with hops = 0 does) and writes nothing.  To leave a stream alone, do not list it.
+ *
+ * Both calls:
+ *   - streams / counts / hops are HOST arrays, free for reuse when the call returns (also for ASP_MEM_DEVICE, where
+ *     the call stays asynchronous on the batch's stream): the batch keeps its own copy of each call's lists in a ring
+ *     of 8 slots (pinned host memory plus device memory, an event per slot).  Up to 8 list calls may be in flight; a
+ *     ninth BLOCKS the host until the call 8 before it has finished on the device, then enqueues as usual;
+ *   - mem applies to the samples; ASP_MEM_HOST copies in and out, returns when done, and changes only the blocks
+ *     below counts[i] of out (FlushList: the floats below hops[i] * half of a row);
+ *   - max_blocks may exceed 64: the call is cut into launches of at most 64 macroblocks of each entry, in block order
+ *     per entry; n == 0 or max_blocks == 0 is ASP_OK and enqueues nothing.  FlushList: only n == 0 does nothing,
+ *     max_hops == 0 with n > 0 still consumes the listed overlap tails (in / out may then be NULL);
+ *   - out == in works in place; any other overlap of [in, in + max_blocks * n * macro_size) (FlushList: n * max_hops *
+ *     half) with the same range of out is refused;
+ *   - refused before anything is enqueued, the batch left as it was, with ASP_ERR_PARAM (the last-error record has
+ *     the reason): such an overlap, a null pointer, n outside 0 .. num_streams, a stream outside the batch or listed
+ *     twice, a count outside 0 .. max_blocks or hops outside 0 .. max_hops, max_hops outside 0 .. 7, a bad mem;
+ *   - every window the batch accepts: 256 and 1024 samples on the tuned kernel (a workgroup walks its entry's
+ *     macroblocks itself; at 256 samples four entries per workgroup, each to its own count), the other windows,
+ *     every flush, samples that are not 8-byte aligned and ASP_BT_OLD_KERNEL=1 on the plain kernels' list form;
+ *   - list calls neither poll nor publish the hand-off counters and AspBtBatch_SetFlow does not affect them:
+ *     lock-step Denoise / DenoiseBlocks (hand-off build on or off), ResetStream, Export / ImportState and list calls
+ *     interleave freely on one batch, ordered by the batch's stream. */
+int AspBtBatch_DenoiseList(AspBtBatch* b, const int32_t* streams, const int32_t* counts, int n, const float* in,
+                           float* out, int max_blocks, int mem);
+int AspBtBatch_FlushList(AspBtBatch* b, const int32_t* streams, const int32_t* hops, int n, const float* in,
+                         float* out, int max_hops, int mem);
 int AspBtBatch_ExportState(AspBtBatch* b, int stream, AspBtState* out);
 int AspBtBatch_ImportState(AspBtBatch* b, int stream, const AspBtState* in);
 int AspBtBatch_Synchronize(AspBtBatch* b);
+/* The batch's hipStream_t: device-memory calls are enqueued on it (events around them: tools/bt_list_perf.py). */
+void* AspBtBatch_GetStream(AspBtBatch* b);
 int AspBtBatch_TimedSteps(AspBtBatch* b, const float* in, float* out, int blocks_in_ring,
                           int steps, float* elapsed_ms);
 
